@@ -7,9 +7,9 @@ IARC-style grid, shared map (params/map.yaml, 720 landmarks); the full
 reference per-camera path (detector -> RPP -> clustering -> scoring ->
 particle filter -> shifts -> yaw -> publish gate) plus the rig fusion and the
 joint rig Gauss-Newton, batched `--rigs` rigs per step per GPU. Frames are
-synthetic, rendered into HBM before timing (inputs resident in HBM); a second
-leg passes the same frames as pageable host buffers (H2D inside the timed
-region) and is reported beside it as `host_ingest`.
+synthetic, rendered into HBM before timing (inputs resident in HBM); with
+`--full` a second leg passes the same frames as pageable host buffers (H2D
+inside the timed region) and is reported beside it as `host_ingest`.
 
 Other legs (same JSON contract, own metric names):
   --config 4  BASELINE configs[3]: 8-camera 1920x1080 rigs, camera-sharded
@@ -36,11 +36,17 @@ unique-id broadcast and the max-over-ranks time; the data path's collectives
 are the library's own RCCL calls. Config 3 rigs are independent units: each
 rank processes its own batch (weak scaling, no data-path collective).
 
-Also reported (config 3): p50 single-rig latency (host submit -> result,
-device-resident and host frames), the dominant kernel's roofline (HIP events
-on the library stream during the timed region), and the CPU oracle baseline
-timed on this host before the GPU is touched (rank 0, N=1 only): one core and
-all cores (one frame stream per thread).
+A plain config-3 run sets up, warms up, times the `--steps` steps and prints
+the result line (value, ms_per_step and what the timed steps themselves give).
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's rig and
+camera results, one float64 .npy per record field); the frames, the map and
+the cv::RNG seed are fixed, so the same arguments give the same inputs.
+
+With `--full` (config 3) also reported: p50 single-rig latency (host submit ->
+result, device-resident and host frames), the host-ingest leg, the dominant
+kernel's roofline (HIP events on the library stream during the timed region),
+and the CPU oracle baseline timed on this host before the GPU is touched
+(rank 0, N=1 only): one core and all cores (one frame stream per thread).
 """
 import argparse
 import ctypes as C
@@ -82,6 +88,13 @@ def parse():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--config", type=int, default=3, choices=(2, 3, 4, 5))
+    p.add_argument("--full", action="store_true",
+                   help="config 3: beside the headline figure also the CPU oracle baseline, the p50 single-rig "
+                        "latencies, the host-ingest leg and the per-stage / roofline figures (stage events on during "
+                        "the timed steps, one isolated step after them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="config 3: after the timed steps write what the last timed step returned (every rig result "
+                        "and camera result of the step, in step order) as DIR/<name>.npy, float64")
     p.add_argument("--stream-frames", type=int, default=1000,
                    help="config 2: frames of the single-camera stream (mantis_process per frame)")
     p.add_argument("--stream-batch", type=int, default=250,
@@ -99,11 +112,12 @@ def parse():
     p.add_argument("--contexts4", type=int, default=0,
                    help="config 4: library contexts per rank (each with its own RCCL communicator and host thread); "
                         "0 = 4 at one rank, 1 otherwise")
-    p.add_argument("--latency-iters", type=int, default=32)
+    p.add_argument("--latency-iters", type=int, default=32,
+                   help="single-rig calls of each p50 latency figure (config 3: with --full)")
     p.add_argument("--ingest-steps", type=int, default=1,
-                   help="config 3: timed steps of the host-ingest leg (pageable host frames); 0 = skip")
+                   help="config 3 --full: timed steps of the host-ingest leg (pageable host frames); 0 = skip")
     p.add_argument("--cpu-seconds", type=float, default=8.0,
-                   help="CPU baseline: seconds of oracle work per leg (1 core, all cores)")
+                   help="--full CPU baseline: seconds of oracle work per leg (1 core, all cores)")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="CPU baseline all-cores leg: threads (0 = one frame stream per visible host CPU, "
                         "BASELINE.md §3)")
@@ -111,7 +125,7 @@ def parse():
                    help="GPU_MAX_HW_QUEUES for this process (default 4 per context, at most 32: each context has "
                         "a compute and a copy stream, and streams that share a hardware queue serialise; measured "
                         "at 4 contexts: 8 / 16 / 32 queues -> 15.5k / 16.0k / 15.8k rig poses/s)")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--gn", type=int, default=1,
                    help="joint rig Gauss-Newton after the per-camera pipeline (SURVEY §8 d configs 3/4); "
                         "0 = reference-parity only")
@@ -287,6 +301,23 @@ def cpu_model():
     return "unknown"
 
 
+def dump_outputs(out_dir, batches):
+    """What the last step's mantis_process_batch calls returned, the contexts'
+    shares in step order: one float64 array per field of mantis_result
+    (rig_<field>.npy, one row per rig) and of mantis_cam_result
+    (cam_<field>.npy, one row per camera frame). The 64-bit cv::RNG state is
+    split into its high and low 32 bits so that float64 holds it exactly.
+    6144 rigs x 4 cameras come to 16 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    for prefix, arrs in (("rig", [b.out for b in batches]), ("cam", [b.cam_out for b in batches])):
+        rec = np.concatenate([np.frombuffer(x, dtype=np.dtype(x._type_)) for x in arrs])
+        for name in rec.dtype.names:
+            v = rec[name]
+            if v.dtype == np.uint64:
+                v = np.stack([v >> np.uint64(32), v & np.uint64(0xFFFFFFFF)], axis=1)
+            np.save(os.path.join(out_dir, f"{prefix}_{name}.npy"), np.ascontiguousarray(v, np.float64))
+
+
 # ------------------------------------------------------------- CPU baseline
 def cpu_baseline(a, W, H, cams_per_rig):
     """The oracle (C++17 -O3 restatement of the reference path, test
@@ -422,21 +453,23 @@ def run_config3(a, rk, cpu):
 
     run_steps(batches, a.warmup)
 
-    # ---- timed region: stage / kernel events on every context's stream; host
-    # CPU time of this process (every context's host thread, the cv::RNG draw
-    # threads, the driver's) over the same region
+    # ---- timed region: with --full, stage / kernel events on every context's
+    # stream; host CPU time of this process (every context's host thread, the
+    # cv::RNG draw threads, the driver's) over the same region
     for mc in ctxs:
-        mc.set_profiling(True)
+        mc.set_profiling(a.full)
     barrier_sync()
     cpu0 = os.times()
     t0 = time.perf_counter()
-    run_steps(batches, a.steps, record=True)
+    run_steps(batches, a.steps, record=a.full)
     barrier_sync()
     el_local = time.perf_counter() - t0
     cpu1 = os.times()
     elapsed = rk.max(el_local)
     for mc in ctxs:
         mc.set_profiling(False)
+    if a.dump_outputs and rk.rank == 0:
+        dump_outputs(a.dump_outputs, batches)
     host_cpu_s = (cpu1.user - cpu0.user) + (cpu1.system - cpu0.system)
     value = a.rigs * a.steps * rk.world / elapsed
     ms_per_step = elapsed / a.steps * 1e3
@@ -444,6 +477,38 @@ def run_config3(a, rk, cpu):
     scored = a.steps * sum(c.n_scored for b in batches for c in b.cam_out)
     published = a.steps * sum(r.publish for b in batches for r in b.out)
     published_all = rk.sum(published)  # every rank's published rigs
+    # the result line of a plain run: what the timed steps themselves give
+    line = {
+        "metric": METRIC3,
+        "value": round(value, 3), "unit": "rig poses/s", "n_gpus": rk.world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+        "data": f"synthetic fisheye grid frames rendered in HBM (SURVEY §8d scene, {a.distinct} distinct rigs "
+                f"= {nd * fb / 1e9:.2f} GB cycled), map.yaml landmarks",
+        "config": {"workload": "config3: 4-cam 1280x720 rig, shared map, full mantis3 path per camera"
+                               + (" + joint rig Gauss-Newton" if a.gn else ""),
+                   "rigs_per_step_per_gpu": a.rigs, "cams_per_rig": CAMS, "frames_per_step_per_gpu": n_frames,
+                   "contexts_per_gpu": nctx, "resolution": [W, H], "landmarks": LANDMARKS,
+                   "parallelism": f"rig-data-parallel x{rk.world}"},
+        "ranks_seen": rk.seen(),
+        "camera_frames_per_s": round(value * CAMS, 2),
+        "published_frac": round(published / max(1, a.rigs * a.steps), 4),
+        # SURVEY §8(d)'s "pose" = one published rig pose (the publish gate,
+        # PosePub.h:16): the same timed region, counting only rigs whose
+        # result passed the gate (why `value` counts every rig)
+        "published_rig_poses_per_s": round(published_all / elapsed, 3),
+        "host_cpu_s_per_step": round(host_cpu_s / a.steps, 4),
+        "host_cpu_note": ("process user+system CPU seconds per step over the timed region (os.times: every "
+                          "context's host thread incl. the cv::RNG gaussian draws); / ms_per_step = cores busy"),
+        "host_cores_busy": round(host_cpu_s / el_local, 3),
+        "lib_sha16": lib_sha16(),
+        "src_sha16": src_sha16(),
+    }
+    if not a.full:
+        pool.shutdown()
+        for mc in ctxs:
+            mc.close()
+        return line if rk.rank == 0 else None
 
     # ---- per-step work counts (every step processes the same frames, so the
     # counters of the last step describe each step): ObjPose iterations of the
@@ -650,47 +715,21 @@ def run_config3(a, rk, cpu):
     if a.ingest_steps > 0:
         del hb
 
-    line = None
-    if rk.rank == 0:
-        line = {
-            "metric": METRIC3,
-            "value": round(value, 3), "unit": "rig poses/s", "n_gpus": rk.world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": f"synthetic fisheye grid frames rendered in HBM (SURVEY §8d scene, {a.distinct} distinct rigs "
-                    f"= {nd * fb / 1e9:.2f} GB cycled), map.yaml landmarks",
-            "config": {"workload": "config3: 4-cam 1280x720 rig, shared map, full mantis3 path per camera"
-                                   + (" + joint rig Gauss-Newton" if a.gn else ""),
-                       "rigs_per_step_per_gpu": a.rigs, "cams_per_rig": CAMS, "frames_per_step_per_gpu": n_frames,
-                       "contexts_per_gpu": nctx, "resolution": [W, H], "landmarks": LANDMARKS,
-                       "parallelism": f"rig-data-parallel x{rk.world}"},
-            "ranks_seen": rk.seen(),
-            "p50_latency_ms": round(p50, 3),
-            "p50_latency_rig0_ms": round(p50_rig0, 3),
-            "p50_note": f"one call per rig over {max(1, min(a.distinct, a.latency_iters))} distinct rigs "
-                        f"(rig0: rig 0 repeated {a.latency_iters} times, the rounds 1-5 measure)",
-            "camera_frames_per_s": round(value * CAMS, 2),
-            "published_frac": round(published / max(1, a.rigs * a.steps), 4),
-            # SURVEY §8(d)'s "pose" = one published rig pose (the publish gate,
-            # PosePub.h:16): the same timed region, counting only rigs whose
-            # result passed the gate (why `value` counts every rig)
-            "published_rig_poses_per_s": round(published_all / elapsed, 3),
-            "path_alg_GBps": round(path_bytes * a.steps / elapsed / 1e9, 3),
-            "host_cpu_s_per_step": round(host_cpu_s / a.steps, 4),
-            "host_cpu_note": ("process user+system CPU seconds per step over the timed region (os.times: every "
-                              "context's host thread incl. the cv::RNG gaussian draws); / ms_per_step = cores busy"),
-            "host_cores_busy": round(host_cpu_s / el_local, 3),
-            "lib_sha16": digest,
-            "src_sha16": src_digest,
-            "host_ingest": ingest,
-            "roofline": roof,
-            "roofline_frontend": roof_front,
-            "cpu_baseline": cpu,
-        }
+    line.update({
+        "p50_latency_ms": round(p50, 3),
+        "p50_latency_rig0_ms": round(p50_rig0, 3),
+        "p50_note": f"one call per rig over {max(1, min(a.distinct, a.latency_iters))} distinct rigs "
+                    f"(rig0: rig 0 repeated {a.latency_iters} times, the rounds 1-5 measure)",
+        "path_alg_GBps": round(path_bytes * a.steps / elapsed / 1e9, 3),
+        "host_ingest": ingest,
+        "roofline": roof,
+        "roofline_frontend": roof_front,
+        "cpu_baseline": cpu,
+    })
     pool.shutdown()
     for mc in ctxs:
         mc.close()
-    return line
+    return line if rk.rank == 0 else None
 
 
 # -------------------------------------------------------------------- config 4
@@ -1019,8 +1058,11 @@ def main():
     except ValueError:
         env_q = 4
     os.environ["GPU_MAX_HW_QUEUES"] = str(min(32, max(4, env_q, a.hw_queues)))
+    if a.dump_outputs and a.config != 3:
+        print("bench: --dump-outputs is for config 3", file=sys.stderr)
+        return 2
     cpu = None
-    if a.config == 3 and world == 1 and not a.no_cpu:
+    if a.full and a.config == 3 and world == 1 and not a.no_cpu:
         try:
             cpu = cpu_baseline(a, 1280, 720, 4)  # before any GPU work: nothing else runs on the host cores
         except Exception as e:  # the oracle is optional on a box without it

@@ -257,6 +257,7 @@ def test_bench_launcher_spawns_ranks():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"  # on a host with GPUs too, the ranks see none and stop at context creation
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--no-cpu"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 1

@@ -1,12 +1,12 @@
 #!/bin/bash
 # GPU box: one-context stage / kernel times (1024 rigs = 4096 frames per launch)
 # of the in-tree library and of alternative builds, twice each, alternating.
-# usage: tools/ab_kern.sh [lib.so ...]   (env BARGS: extra bench args)
+# usage: tools/ab_kern.sh [lib.so ...]   (env BARGS: extra bench args; results under $OUT, default bench_out)
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; mkdir -p gpurun_out
+R=$(cd "$(dirname "$0")/.." && pwd); cd "$R"; OUT=${OUT:-bench_out}; mkdir -p $OUT
 run() {
-  MANTIS_AMD_LIB=$1 timeout -k 10 200 python -u bench.py --contexts 1 --rigs 1024 --steps 3 --warmup 1 --latency-iters 3 --no-cpu --ingest-steps 0 $BARGS > gpurun_out/abk_$2.json 2> gpurun_out/abk_$2.err || { tail -5 gpurun_out/abk_$2.err; exit 1; }
-  python3 - gpurun_out/abk_$2.json $2 <<'P'
+  MANTIS_AMD_LIB=$1 timeout -k 10 200 python -u bench.py --full --contexts 1 --rigs 1024 --steps 3 --warmup 1 --latency-iters 3 --no-cpu --ingest-steps 0 $BARGS > $OUT/abk_$2.json 2> $OUT/abk_$2.err || { tail -5 $OUT/abk_$2.err; exit 1; }
+  python3 - $OUT/abk_$2.json $2 <<'P'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]
