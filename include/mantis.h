@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MANTIS_ABI_VERSION 2
+#define MANTIS_ABI_VERSION 3
 
 typedef enum mantis_status {
   MANTIS_OK = 0,
@@ -389,6 +389,76 @@ int32_t mantis_frame_counters(void* ctx, int32_t frame, int32_t* out, int32_t ma
  * throughput kernels; both give identical results (CUs / 4 by default,
  * MANTIS_FC_SMALL_FRAMES). No reference counterpart: a tuning query. */
 int32_t mantis_small_batch_frames(void* ctx);
+
+/* ------------------------------------------------- rig tracking (ABI 3) */
+/* Joint multi-camera particle filter from a pose prior: the reference's
+ * particle filter (optimizeHypothesisWithParticleFilter, PoseAdjustment.h:13-60)
+ * seeded from a predicted rig pose instead of from detection, its particles
+ * rig base poses T_w_b, each scored on every camera of the rig with the sums
+ * pooled (the mantisService's "delta applied to each particle before
+ * reevaluating", srv/mantisService.srv:4-8; MonteCarlo.cpp:250's "TODO make
+ * work with both cameras"). Only the image stages up to the cleanImageByEdge
+ * mask run: no contours, RPP, hypothesis generation, shifts or yaw sets.
+ *
+ * Pooled error of a base pose T: for each camera c the fast WHITE evaluator
+ * (HypothesisEvaluation.h:107-158, 218-227) on c's cleaned frame with
+ * c2w_c = inverse(T * T_base_cam_c) gives exact integers (sum_c, n_c);
+ * E = (double)sum(sum_c) / ((double)sum(n_c) * 1.1), DBL_MAX when sum(n_c) = 0.
+ * cur = the prediction, iter_err[0] = seed_error = E(cur). Iteration k = 1 ..
+ * iterations: particle j = cur * rand_j, rand_j = Transform(setRPY(roll,
+ * pitch, yaw), (x, y, z)) from six gaussians of the context's cv::RNG drawn
+ * yaw, pitch, roll (x sigma_rot), z, y, x (x sigma_t), applied on the right
+ * in the base frame; the first strict minimum (argmin by (E, j)) replaces cur
+ * only when it is < the current error; iter_pick[k-1] = that j or -1,
+ * iter_err[k] = the current error afterwards. Every rig draws particles x
+ * iterations x 6 gaussians, rigs in order, tracked or not. */
+typedef struct mantis_track_params {
+  int32_t struct_size;      /* sizeof(mantis_track_params) */
+  int32_t particles;        /* 1..96 */
+  int32_t iterations;       /* 0..10; 0 = score the prediction only */
+  double sigma_rot, sigma_t; /* >= 0 (sigma_rot <= 1e6); 0 is legal (particles equal the current pose) */
+  int32_t min_projections;  /* gate: pooled in-frame landmark count, default 10 (MonteCarlo.cpp:220) */
+  int32_t record;           /* 1 = keep the per-iteration record (mantis_get_track_record) */
+  double max_error;         /* gate: <= 0 means none */
+} mantis_track_params;
+/* 50 / 10 / 0.03 / 0.01 (cfg.particles / cfg.iterations when ctx is given and they fit), 10, 0, 0 */
+void mantis_default_track_params(void* ctx /* nullable */, mantis_track_params* p);
+
+typedef struct mantis_track_result {
+  int32_t status, tracked, n_proj, n_scored; /* n_proj = sum(n_c) at T_w_b; n_scored = 1 + particles x iterations */
+  double T_w_b[16];         /* refined base pose, row-major */
+  double error, seed_error; /* pooled fast error after / of the prediction */
+  double iter_err[11];      /* [0] = seed, [k] = current error after iteration k (k > iterations: = error) */
+  int32_t iter_pick[10];    /* [k-1] = particle accepted in iteration k, -1 = none (also past `iterations`) */
+  uint64_t rng_state_after; /* cv::RNG state after this rig's draws */
+} mantis_track_result;
+/* sizeof(mantis_track_params), sizeof(mantis_track_result) (host only) */
+void mantis_track_sizes(int32_t* params_bytes, int32_t* result_bytes);
+
+/* n_rigs rigs of cams_per_rig cameras (cams[r * cams_per_rig + c], one frame
+ * size), rig r refined from T_w_b_pred[r] (n_rigs x 16, row-major).
+ * tracked = error != DBL_MAX && n_proj >= min_projections && (max_error <= 0
+ * || error <= max_error). MANTIS_ERR_ARG (nothing launched): no map, n_rigs x
+ * cams_per_rig > max_cams, cams_per_rig > 8, particles x cams_per_rig > 512,
+ * frames of different sizes, a parameter outside its range. */
+mantis_status mantis_track_batch(void* ctx, const mantis_image* cams, int32_t n_rigs, int32_t cams_per_rig,
+                                 const double* T_w_b_pred, const mantis_track_params* p, mantis_track_result* out);
+/* One rig from the context's prior (mantis_set_prior_pose / the last published
+ * pose): prediction = prior * Transform(delta_quat, delta_pos), the prior
+ * itself when motion is NULL or unset (|q|^2 < 0.5). MANTIS_ERR_STATE without
+ * a prior. Tracked: the prior becomes T_w_b and out is a published rig
+ * (publish = 1, pose from T_w_b, covariance = diag(error / 600), weight =
+ * error, num_particles = n_scored). Not tracked: publish = 0, the prior stays;
+ * the caller falls back to mantis_process. tout (nullable) gets the details. */
+mantis_status mantis_track(void* ctx, const mantis_image* cams, int32_t n_cams, const mantis_motion* motion,
+                           const mantis_track_params* p, mantis_result* out, mantis_track_result* tout);
+/* Record of rig `rig` of the last track call made with record = 1: iteration
+ * k = 1 .. iterations, or -1 = the seed (one "particle", the prediction).
+ * T_w_b: P x 16, c2w: P x C x 12 (world -> camera R row-major | t), sums /
+ * counts: P x C integer error sums and landmark counts; each nullable.
+ * *n_particles = P of that pass (1 for the seed). */
+mantis_status mantis_get_track_record(void* ctx, int32_t rig, int32_t iteration, double* T_w_b, double* c2w,
+                                      int64_t* sums, int32_t* counts, int32_t* n_particles);
 
 #ifdef __cplusplus
 }

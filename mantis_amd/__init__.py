@@ -60,6 +60,18 @@ class MantisRigGnInfo(C.Structure):
                 ("n_obs_local", C.c_int32)]
 
 
+class MantisTrackParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("particles", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_rot", C.c_double), ("sigma_t", C.c_double), ("min_projections", C.c_int32),
+                ("record", C.c_int32), ("max_error", C.c_double)]
+
+
+class MantisTrackResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("tracked", C.c_int32), ("n_proj", C.c_int32), ("n_scored", C.c_int32),
+                ("T_w_b", C.c_double * 16), ("error", C.c_double), ("seed_error", C.c_double),
+                ("iter_err", C.c_double * 11), ("iter_pick", C.c_int32 * 10), ("rng_state_after", C.c_uint64)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -154,6 +166,15 @@ _SIGS = {
     "mantis_get_rig_weights_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mantis_shard_gauss_offsets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                              C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "mantis_default_track_params": (None, [C.c_void_p, C.POINTER(MantisTrackParams)]),
+    "mantis_track_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_track_batch": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32, C.c_void_p,
+                                     C.POINTER(MantisTrackParams), C.POINTER(MantisTrackResult)]),
+    "mantis_track": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.POINTER(MantisMotion),
+                               C.POINTER(MantisTrackParams), C.POINTER(MantisResult),
+                               C.POINTER(MantisTrackResult)]),
+    "mantis_get_track_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.c_int32)]),
 }
 
 
@@ -366,6 +387,73 @@ class Mantis:
         else:
             T = np.ascontiguousarray(T, np.float64)
             self._chk(lib().mantis_set_prior_pose(self.h, T.ctypes.data), "set_prior_pose")
+
+    # rig tracking (mantis_track*, include/mantis.h) -------------------------
+    def track_params(self, **params):
+        """mantis_default_track_params for this context, then the overrides."""
+        p = MantisTrackParams()
+        lib().mantis_default_track_params(self.h, C.byref(p))
+        for k, v in params.items():
+            if k not in dict(MantisTrackParams._fields_) or k == "struct_size":
+                raise TypeError(f"track: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def track_batch(self, images, rigs, T_pred, **params):
+        """mantis_track_batch: `rigs` rigs (images rig-major) refined from the
+        predicted base poses T_pred (rigs x 4 x 4); returns the rigs'
+        MantisTrackResult records."""
+        n = len(images)
+        assert rigs > 0 and n % rigs == 0
+        cams = (MantisImage * n)(*images)
+        T = np.ascontiguousarray(T_pred, np.float64).reshape(-1)
+        assert T.size == 16 * rigs
+        p = self.track_params(**params)
+        out = (MantisTrackResult * rigs)()
+        self._track_cams = n // rigs
+        st = lib().mantis_track_batch(self.h, cams, rigs, n // rigs, T.ctypes.data, C.byref(p), out)
+        self._chk(st, "track_batch")
+        return list(out)
+
+    def track(self, images, delta_pos=None, delta_quat_xyzw=None, **params):
+        """mantis_track: one rig from the context's prior pose and an optional
+        mantisService motion; returns (MantisResult, MantisTrackResult).
+        result.publish == 0: not tracked, fall back to process_motion()."""
+        n = len(images)
+        cams = (MantisImage * n)(*images)
+        mo = None
+        if delta_pos is not None:
+            mo = MantisMotion()
+            for i in range(3):
+                mo.delta_pos[i] = delta_pos[i]
+            for i in range(4):
+                mo.delta_quat_xyzw[i] = delta_quat_xyzw[i]
+        p = self.track_params(**params)
+        out = MantisResult()
+        tout = MantisTrackResult()
+        self._track_cams = n
+        st = lib().mantis_track(self.h, cams, n, None if mo is None else C.byref(mo), C.byref(p), C.byref(out),
+                                C.byref(tout))
+        self._chk(st, "track")
+        return out, tout
+
+    def track_record(self, rig, iteration):
+        """Record of rig `rig` of the last track call made with record=1
+        (mantis_get_track_record), iteration 1 .. iterations or -1 = the seed:
+        (T_w_b [P, 4, 4], c2w [P, C, 12], sums [P, C] int64, counts [P, C] int32)."""
+        Cn = getattr(self, "_track_cams", None)
+        if Cn is None:
+            raise MantisError("track_record: no track call on this context")
+        T = np.zeros((96, 16))  # the record's particle count is at most 96
+        c2w = np.zeros(96 * Cn * 12)
+        sums = np.zeros(96 * Cn, np.int64)
+        cnt = np.zeros(96 * Cn, np.int32)
+        npart = C.c_int32()
+        self._chk(lib().mantis_get_track_record(self.h, rig, iteration, T.ctypes.data, c2w.ctypes.data,
+                                                sums.ctypes.data, cnt.ctypes.data, C.byref(npart)), "get_track_record")
+        P = npart.value
+        return (T[:P].reshape(P, 4, 4).copy(), c2w[: P * Cn * 12].reshape(P, Cn, 12).copy(),
+                sums[: P * Cn].reshape(P, Cn).copy(), cnt[: P * Cn].reshape(P, Cn).copy())
 
     def process_sharded(self, images, rigs, cam_index, cams_per_rig):
         """Camera-sharded rig call (mantis_process_rig_sharded): images are this

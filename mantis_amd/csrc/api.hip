@@ -283,6 +283,22 @@ struct Ctx {
   // off (every landmark takes the exact FP64 fallback; a test / A-B switch)
   bool screen_off = false;
   std::vector<std::pair<Cam, ScreenCam>> scam_cache;  // screen_cam_cached
+  // rig tracking (track_impl.hip): workspaces allocated on first use and grown
+  // to the largest call, and the last call's shape (mantis_get_track_record)
+  struct Track {
+    void* d_in = nullptr;   // predictions, extrinsics, gaussians (one H2D copy from h_in)
+    void* h_in = nullptr;   // pinned
+    size_t in_cap = 0;
+    void* d_state = nullptr;  // per rig: current pose and error between the launches
+    void* d_res = nullptr;    // per rig: mantis_track_result
+    void* h_res = nullptr;    // pinned
+    int rig_cap = 0;
+    void *d_Twb = nullptr, *d_c2w = nullptr, *d_pf = nullptr;  // per pass x rig x particle (x camera)
+    long long* d_sums = nullptr;
+    int32_t* d_cnt = nullptr;
+    size_t pose_cap = 0, task_cap = 0;  // entries of d_Twb; of d_c2w / d_pf / d_sums / d_cnt
+    int rigs = 0, C = 0, P = 0, I = 0, record = 0;  // the last call
+  } trk;
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1321,8 +1337,12 @@ mantis_status mantis_destroy(void* ctx) {
                    c->d_dense_c2w, c->d_dense_err, c->d_dense_np, c->d_pairs, c->d_gncam, c->d_rigio, c->d_gnobs, c->d_gnacc, c->d_sh_gidx, c->d_sh_pf, c->d_sh_flags, c->d_sh_rec, c->d_gen, c->d_hyps, c->d_st, c->d_sst, c->d_dbg, c->d_res, c->d_gauss, c->d_gtotal, c->d_lm};
   for (void* p : dptrs)
     if (p) (void)hipFree(p);
+  void* tptrs[] = {c->trk.d_in, c->trk.d_state, c->trk.d_res, c->trk.d_Twb, c->trk.d_c2w, c->trk.d_pf, c->trk.d_sums, c->trk.d_cnt};
+  for (void* p : tptrs)
+    if (p) (void)hipFree(p);
   for (void* p : c->user_allocs) (void)hipFree(p);
-  void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec};
+  void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
+                   c->trk.h_in, c->trk.h_res};
   for (void* p : hptrs)
     if (p) (void)hipHostFree(p);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -2166,4 +2186,5 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "gn_impl.hip"
 #include "dense_impl.hip"
 #include "markov_impl.hip"
+#include "track_impl.hip"
 #include "ros_wire.h"

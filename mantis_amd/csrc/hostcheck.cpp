@@ -20,6 +20,7 @@ static int g_jacobi_ff = 1;
 #include "mk_screen.h"
 #include "mk_shard.h"
 #include "mk_sort.h"
+#include "mk_track.h"
 
 extern "C" {
 
@@ -383,6 +384,31 @@ void hc_quad_gn(int n, double* R, double* t, const double* img, const double* ob
                 double* cost0, double* cost) {
   for (int i = 0; i < n; i++)
     steps[i] = mk::quad_gn_refine(R + 9 * i, t + 3 * i, img + 8 * i, obj + 12 * i, iters, cost0 + i, cost + i);
+}
+
+// rig tracking (mk_track.h): the rules k_track_particles runs, one call each.
+// sums / counts: n_particles x n_cams; err / n_proj: one entry per particle
+void hc_track_pool(const int64_t* sums, const int32_t* counts, int n_particles, int n_cams, double* err,
+                   int32_t* n_proj) {
+  for (int j = 0; j < n_particles; j++) {
+    long long s[mk::track::kMaxCams];
+    for (int c = 0; c < n_cams && c < mk::track::kMaxCams; c++) s[c] = sums[(size_t)j * n_cams + c];
+    err[j] = mk::track::pool(s, counts + (size_t)j * n_cams, n_cams < mk::track::kMaxCams ? n_cams : mk::track::kMaxCams,
+                             &n_proj[j]);
+  }
+}
+int hc_track_pick(const double* err, int n, double cur_err) { return mk::track::pick(err, n, cur_err); }
+int hc_track_gate(double error, int32_t n_proj, int32_t min_projections, double max_error) {
+  return mk::track::gate(error, n_proj, min_projections, max_error);
+}
+// particle = T_w_b * rand(g6) and its world -> camera pose through T_base_cam (row-major 4x4 in, 4x4 / 12 out)
+void hc_track_particle(const double* T_w_b, const float* g6, double sigma_rot, double sigma_t, const double* T_base_cam,
+                       double* T_out, double* c2w12) {
+  const mk::Xf T = mk::track::particle(mk::track::xf_from_mat4(T_w_b), g6, sigma_rot, sigma_t);
+  mk::track::xf_to_mat4(T, T_out);
+  const mk::Xf v = mk::track::cam_c2w(T, mk::track::xf_from_mat4(T_base_cam));
+  std::memcpy(c2w12, v.R, sizeof(double) * 9);
+  std::memcpy(c2w12 + 9, v.t, sizeof(double) * 3);
 }
 
 }  // extern "C"
