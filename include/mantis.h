@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MANTIS_ABI_VERSION 3
+#define MANTIS_ABI_VERSION 4
 
 typedef enum mantis_status {
   MANTIS_OK = 0,
@@ -459,6 +459,105 @@ mantis_status mantis_track(void* ctx, const mantis_image* cams, int32_t n_cams, 
  * *n_particles = P of that pass (1 for the seed). */
 mantis_status mantis_get_track_record(void* ctx, int32_t rig, int32_t iteration, double* T_w_b, double* c2w,
                                       int64_t* sums, int32_t* counts, int32_t* n_particles);
+
+/* ---------------------------------------- Monte Carlo localization (ABI 4) */
+/* A persistent, weighted, resampled population of rig base poses T_w_b in the
+ * context's HBM: the filter the mantisService contract implies (delta_pos /
+ * delta_quat "applied to each particle before reevaluating", weight,
+ * num_particles; srv/mantisService.srv) and the legacy MonteCarlo.cpp never
+ * became. One filter per context. One step (mantis_mcl_step), exactly:
+ *  1. Draws: N x 6 gaussians of the context's cv::RNG, particle-major, each
+ *     particle's six drawn yaw, pitch, roll, z, y, x (as mantis_track), then
+ *     one raw 32-bit output U (state = (uint32)state * 4164903690 + (state >>
+ *     32), U = (uint32)state): on every step, whatever the sigmas and outcome.
+ *  2. Predict: T_j <- T_j * Delta * rand_j(sigma_rot, sigma_t), Delta =
+ *     Transform(delta_quat, delta_pos), the identity when motion is NULL or
+ *     unset (|q|^2 < 0.5); everything applied on the right.
+ *  3. Score: the image stages up to the cleanImageByEdge mask, then for every
+ *     (particle, camera) the exact integers (sum, n) of the fast WHITE
+ *     evaluator with c2w = inverse(T_j * T_base_cam_c); E_j = the pooled error
+ *     of mantis_track. Particle j is valid iff E_j != DBL_MAX and n_j >=
+ *     min_projections.
+ *  4. Weights in fixed point: L_j <- L_j - E_j / tau (valid), -inf (others);
+ *     Lmax = max L_j; q_j = (uint64)floor(exp(L_j - Lmax) * 2^40) (0 for L_j =
+ *     -inf); S = sum q_j and the inclusive sums c_j are exact integers, the same
+ *     in any reduction order. No particle with a finite L_j: the step is lost
+ *     (lost = 1, out->publish = 0, the particles keep their predicted poses
+ *     and their previous log-weights, nothing is resampled, the context's
+ *     prior pose is untouched).
+ *  5. Estimate: w_j = q_j / S; position sum w_j t_j; rotation = the normalised
+ *     w-weighted sum of the particles' quaternions (Matrix3x3::getRotation),
+ *     each with the sign that has a non-negative dot with particle best's --
+ *     best's own basis if that sum's norm is < 1e-12 or only one particle has
+ *     q > 0; covariance = sum w_j xi_j xi_j^T, xi_j = [t_j - t ; log(R^T R_j)],
+ *     order x, y, z, rot-x, rot-y, rot-z row-major (ROS PoseWithCovariance;
+ *     translation in the world frame, rotation a right perturbation);
+ *     ess = S^2 / sum q_j^2; best = the heaviest particle, the first on ties.
+ *  6. Resample iff ess < resample_frac * N: systematic, ancestor a_i = the
+ *     first j with c_j N 2^32 > (U + i 2^32) S in exact integer arithmetic,
+ *     clamped to the last particle with q > 0; new particle i = old particle
+ *     a_i, every L = 0. Otherwise the poses and the L_j stay.
+ *  7. Output (not lost): publish = 1, the pose and the 6 x 6 covariance of the
+ *     estimate, weight = best_error, num_particles = N; the context's prior
+ *     pose becomes the estimate (mantis_track / mantis_process with a motion
+ *     can take over).
+ * Default tau: the median over 32 four-camera 720p synthetic rigs of
+ * E(truth moved 2 cm and 1 degree) - E(truth), so that a particle that far
+ * off keeps about 1/e of the best weight. Measured on an MI355X with
+ * tools/mcl_latency.py: median 63478 (quartiles 59181 / 69064, range 46559 ..
+ * 76800; E(truth) itself has the median 19658). DESIGN.md 4b. */
+#define MANTIS_MCL_TAU_DEFAULT 63478.0
+typedef struct mantis_mcl_params {
+  int32_t struct_size;        /* sizeof(mantis_mcl_params) */
+  int32_t n_particles;        /* 1..4096 */
+  double sigma_rot, sigma_t;  /* per-step diffusion, >= 0 (sigma_rot <= 1e6), finite */
+  double tau;                 /* > 0, finite: log-likelihood = -E / tau */
+  double resample_frac;       /* 0..2: resample when ess < resample_frac * N (0 = never, 2 = always) */
+  int32_t min_projections;    /* a particle with fewer pooled in-frame landmarks gets weight 0 */
+  int32_t record;             /* 1 = keep the last step's record (mantis_mcl_get_record) */
+} mantis_mcl_params;
+/* 256 / 0.03 / 0.01 / MANTIS_MCL_TAU_DEFAULT / 0.5 / 10 / 0 */
+void mantis_default_mcl_params(mantis_mcl_params* p);
+
+typedef struct mantis_mcl_result {
+  int32_t status, lost, resampled, n_particles;
+  int32_t n_valid, best;      /* particles with q > 0; the heaviest one (first on ties), -1 when lost */
+  double ess, best_error;     /* S^2 / sum q^2; E of particle best (0 / DBL_MAX when lost) */
+  double T_w_b[16];           /* the estimate, row-major (zeros when lost) */
+  double covariance[36];
+  uint64_t weight_sum;        /* S */
+  uint32_t U, pad;            /* the resampling draw */
+  uint64_t rng_state_after;
+} mantis_mcl_result;
+/* sizeof(mantis_mcl_params), sizeof(mantis_mcl_result) (host only) */
+void mantis_mcl_sizes(int32_t* params_bytes, int32_t* result_bytes);
+
+/* Start the filter: particle j = T_w_b_mean * rand_j(sigma_rot0, sigma_t0)
+ * from N x 6 gaussians drawn as in a step (and nothing else), every L = 0.
+ * MANTIS_ERR_ARG (the filter and the RNG stay as they were): a parameter
+ * outside its range, a null pointer, a NaN. */
+mantis_status mantis_mcl_init(void* ctx, const double* T_w_b_mean, double sigma_rot0, double sigma_t0,
+                              const mantis_mcl_params* p);
+/* The same from given poses (N x 16, row-major); draws nothing. */
+mantis_status mantis_mcl_init_particles(void* ctx, const double* T_w_b, const mantis_mcl_params* p);
+/* One step on n_cams synchronized cameras of one size (1..8, <= max_cams).
+ * MANTIS_ERR_STATE before an init; MANTIS_ERR_ARG (nothing launched, nothing
+ * drawn): no map, frames of different sizes, n_cams out of range, a NaN
+ * motion. mout is nullable. */
+mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cams, const mantis_motion* motion,
+                              mantis_result* out, mantis_mcl_result* mout);
+/* The particles as they stand: T_w_b (N x 16) and log_w (N) nullable, *n = N. */
+mantis_status mantis_mcl_get(void* ctx, double* T_w_b, double* log_w, int32_t* n);
+/* The last step's record (params.record = 1), each pointer nullable: the
+ * predicted T_w_b (N x 16), c2w (N x C x 12, world -> camera R row-major | t),
+ * sums / counts (N x C), L before and after the step (N each), q and cum (N
+ * uint64; zeros when lost), ancestors (N int32, -1 each when not resampled),
+ * *n_particles = N, *n_cams = C. */
+mantis_status mantis_mcl_get_record(void* ctx, double* T_w_b_pred, double* c2w, int64_t* sums, int32_t* counts,
+                                    double* L_before, double* L_after, uint64_t* q, uint64_t* cum,
+                                    int32_t* ancestors, int32_t* n_particles, int32_t* n_cams);
+/* Drop the filter (the next step needs an init); draws nothing. */
+mantis_status mantis_mcl_reset(void* ctx);
 
 #ifdef __cplusplus
 }

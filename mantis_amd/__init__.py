@@ -72,6 +72,19 @@ class MantisTrackResult(C.Structure):
                 ("iter_err", C.c_double * 11), ("iter_pick", C.c_int32 * 10), ("rng_state_after", C.c_uint64)]
 
 
+class MantisMclParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_particles", C.c_int32), ("sigma_rot", C.c_double),
+                ("sigma_t", C.c_double), ("tau", C.c_double), ("resample_frac", C.c_double),
+                ("min_projections", C.c_int32), ("record", C.c_int32)]
+
+
+class MantisMclResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("lost", C.c_int32), ("resampled", C.c_int32), ("n_particles", C.c_int32),
+                ("n_valid", C.c_int32), ("best", C.c_int32), ("ess", C.c_double), ("best_error", C.c_double),
+                ("T_w_b", C.c_double * 16), ("covariance", C.c_double * 36), ("weight_sum", C.c_uint64),
+                ("U", C.c_uint32), ("pad", C.c_uint32), ("rng_state_after", C.c_uint64)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -175,6 +188,15 @@ _SIGS = {
                                C.POINTER(MantisTrackResult)]),
     "mantis_get_track_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.POINTER(C.c_int32)]),
+    "mantis_default_mcl_params": (None, [C.POINTER(MantisMclParams)]),
+    "mantis_mcl_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_mcl_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.POINTER(MantisMclParams)]),
+    "mantis_mcl_init_particles": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MantisMclParams)]),
+    "mantis_mcl_step": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.POINTER(MantisMotion),
+                                  C.POINTER(MantisResult), C.POINTER(MantisMclResult)]),
+    "mantis_mcl_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "mantis_mcl_get_record": (C.c_int, [C.c_void_p] + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)] * 2),
+    "mantis_mcl_reset": (C.c_int, [C.c_void_p]),
 }
 
 
@@ -454,6 +476,74 @@ class Mantis:
         P = npart.value
         return (T[:P].reshape(P, 4, 4).copy(), c2w[: P * Cn * 12].reshape(P, Cn, 12).copy(),
                 sums[: P * Cn].reshape(P, Cn).copy(), cnt[: P * Cn].reshape(P, Cn).copy())
+
+    # Monte Carlo localization (mantis_mcl_*, include/mantis.h) ---------------
+    def mcl_params(self, **params):
+        """mantis_default_mcl_params, then the overrides."""
+        p = MantisMclParams()
+        lib().mantis_default_mcl_params(C.byref(p))
+        for k, v in params.items():
+            if k not in dict(MantisMclParams._fields_) or k == "struct_size":
+                raise TypeError(f"mcl: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def mcl_init(self, T_mean, sigma_rot0, sigma_t0, **params):
+        """mantis_mcl_init: n_particles draws around the base pose T_mean."""
+        T = np.ascontiguousarray(T_mean, np.float64).reshape(16)
+        p = self.mcl_params(**params)
+        self._chk(lib().mantis_mcl_init(self.h, T.ctypes.data, sigma_rot0, sigma_t0, C.byref(p)), "mcl_init")
+
+    def mcl_init_particles(self, T_w_b, **params):
+        """mantis_mcl_init_particles: the set from given base poses (N x 4 x 4)."""
+        T = np.ascontiguousarray(T_w_b, np.float64).reshape(-1, 16)
+        p = self.mcl_params(n_particles=len(T), **params)
+        self._chk(lib().mantis_mcl_init_particles(self.h, T.ctypes.data, C.byref(p)), "mcl_init_particles")
+
+    def mcl_step(self, images, delta_pos=None, delta_quat_xyzw=None):
+        """mantis_mcl_step: one step on the rig's frames with an optional
+        mantisService motion; returns (MantisResult, MantisMclResult)."""
+        n = len(images)
+        cams = (MantisImage * n)(*images)
+        mo = None
+        if delta_pos is not None:
+            mo = MantisMotion()
+            for i in range(3):
+                mo.delta_pos[i] = delta_pos[i]
+            for i in range(4):
+                mo.delta_quat_xyzw[i] = delta_quat_xyzw[i]
+        out = MantisResult()
+        mout = MantisMclResult()
+        st = lib().mantis_mcl_step(self.h, cams, n, None if mo is None else C.byref(mo), C.byref(out), C.byref(mout))
+        self._chk(st, "mcl_step")
+        return out, mout
+
+    def mcl_particles(self):
+        """mantis_mcl_get: (T_w_b [N, 4, 4], log-weights [N])."""
+        n = C.c_int32()
+        self._chk(lib().mantis_mcl_get(self.h, None, None, C.byref(n)), "mcl_get")
+        T = np.zeros((n.value, 4, 4))
+        L = np.zeros(n.value)
+        self._chk(lib().mantis_mcl_get(self.h, T.ctypes.data, L.ctypes.data, C.byref(n)), "mcl_get")
+        return T, L
+
+    def mcl_record(self):
+        """mantis_mcl_get_record: the last step's record (record=1) as a dict:
+        T_pred [N, 4, 4], c2w [N, C, 12], sums / counts [N, C], L_before /
+        L_after [N], q / cum [N] uint64, ancestors [N] int32."""
+        n, cn = C.c_int32(), C.c_int32()
+        none = [None] * 9
+        self._chk(lib().mantis_mcl_get_record(self.h, *none, C.byref(n), C.byref(cn)), "mcl_get_record")
+        N, Cn = n.value, cn.value
+        r = {"T_pred": np.zeros((N, 4, 4)), "c2w": np.zeros((N, Cn, 12)), "sums": np.zeros((N, Cn), np.int64),
+             "counts": np.zeros((N, Cn), np.int32), "L_before": np.zeros(N), "L_after": np.zeros(N),
+             "q": np.zeros(N, np.uint64), "cum": np.zeros(N, np.uint64), "ancestors": np.zeros(N, np.int32)}
+        self._chk(lib().mantis_mcl_get_record(self.h, *[a.ctypes.data for a in r.values()], C.byref(n), C.byref(cn)),
+                  "mcl_get_record")
+        return r
+
+    def mcl_reset(self):
+        self._chk(lib().mantis_mcl_reset(self.h), "mcl_reset")
 
     def process_sharded(self, images, rigs, cam_index, cams_per_rig):
         """Camera-sharded rig call (mantis_process_rig_sharded): images are this

@@ -299,6 +299,25 @@ struct Ctx {
     size_t pose_cap = 0, task_cap = 0;  // entries of d_Twb; of d_c2w / d_pf / d_sums / d_cnt
     int rigs = 0, C = 0, P = 0, I = 0, record = 0;  // the last call
   } trk;
+  // Monte Carlo localization (mcl_impl.hip): the particle set lives here
+  // between the steps; buffers sized for `cap` particles x 8 cameras, grown
+  // by an init with more particles
+  struct Mcl {
+    bool live = false;          // an init has run (mantis_mcl_reset clears)
+    mantis_mcl_params p{};
+    int N = 0, cap = 0, cur = 0;  // particles, capacity, which of d_T holds the set
+    void* d_T[2] = {nullptr, nullptr};  // Xf x cap: the set and the resampling target
+    double *d_L = nullptr, *d_Lprev = nullptr;  // log-weights; those before the last step
+    unsigned long long *d_q = nullptr, *d_cum = nullptr;
+    int32_t* d_anc = nullptr;
+    void *d_in = nullptr, *h_in = nullptr;  // extrinsics, motion, gaussians (one H2D copy); pinned
+    void *d_c2w = nullptr, *d_pf = nullptr;  // cap x 8
+    long long* d_sums = nullptr;
+    int32_t* d_cnt = nullptr;
+    void *d_res = nullptr, *h_res = nullptr;  // the step's result record; pinned
+    bool has_record = false;  // a step has run since the init
+    int rec_C = 0, rec_pred = 0;  // its cameras; which of d_T holds its predicted poses
+  } mcl;
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1340,9 +1359,13 @@ mantis_status mantis_destroy(void* ctx) {
   void* tptrs[] = {c->trk.d_in, c->trk.d_state, c->trk.d_res, c->trk.d_Twb, c->trk.d_c2w, c->trk.d_pf, c->trk.d_sums, c->trk.d_cnt};
   for (void* p : tptrs)
     if (p) (void)hipFree(p);
+  void* mptrs[] = {c->mcl.d_T[0], c->mcl.d_T[1], c->mcl.d_L, c->mcl.d_Lprev, c->mcl.d_q, c->mcl.d_cum, c->mcl.d_anc,
+                   c->mcl.d_in, c->mcl.d_c2w, c->mcl.d_pf, c->mcl.d_sums, c->mcl.d_cnt, c->mcl.d_res};
+  for (void* p : mptrs)
+    if (p) (void)hipFree(p);
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
-                   c->trk.h_in, c->trk.h_res};
+                   c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res};
   for (void* p : hptrs)
     if (p) (void)hipHostFree(p);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -2187,4 +2210,5 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "dense_impl.hip"
 #include "markov_impl.hip"
 #include "track_impl.hip"
+#include "mcl_impl.hip"
 #include "ros_wire.h"

@@ -16,6 +16,7 @@ static int g_jacobi_ff = 1;
 #include "mk_contour.h"
 #include "mk_gn.h"
 #include "mk_math.h"
+#include "mk_mcl.h"
 #include "mk_rpp.h"
 #include "mk_screen.h"
 #include "mk_shard.h"
@@ -409,6 +410,84 @@ void hc_track_particle(const double* T_w_b, const float* g6, double sigma_rot, d
   const mk::Xf v = mk::track::cam_c2w(T, mk::track::xf_from_mat4(T_base_cam));
   std::memcpy(c2w12, v.R, sizeof(double) * 9);
   std::memcpy(c2w12 + 9, v.t, sizeof(double) * 3);
+}
+
+// Monte Carlo localization (mk_mcl.h): the rules k_mcl_weight / k_mcl_resample run.
+// L <- L - E / tau or -inf, then q = floor(exp(L - Lmax) 2^40); returns 1 when lost (no finite L: q = 0)
+int hc_mcl_weights(const double* L, const double* E, const int32_t* n_proj, int N, double tau, int32_t min_projections,
+                   double* L_out, uint64_t* q) {
+  double Lmax = -INFINITY;
+  for (int j = 0; j < N; j++) {
+    L_out[j] = mk::mcl::log_weight(L[j], E[j], n_proj[j], min_projections, tau);
+    if (L_out[j] > Lmax) Lmax = L_out[j];
+  }
+  for (int j = 0; j < N; j++) q[j] = Lmax > -INFINITY ? mk::mcl::weight_q(L_out[j], Lmax) : 0;
+  return Lmax > -INFINITY ? 0 : 1;
+}
+// the inclusive integer scan, added the way the device block does: lanes of a
+// wave, then waves of a round of 1024, then rounds
+void hc_mcl_scan(const uint64_t* q, int N, uint64_t* cum) {
+  uint64_t carry = 0;
+  for (int r0 = 0; r0 < N; r0 += 1024) {
+    uint64_t wt[16] = {0};
+    for (int w = 0; w < 16; w++) {
+      uint64_t incl = 0;
+      for (int l = 0; l < 64; l++) {
+        const int j = r0 + w * 64 + l;
+        if (j >= N) break;
+        incl += q[j];
+        cum[j] = incl;  // within the wave
+      }
+      wt[w] = incl;
+    }
+    uint64_t pre = carry;
+    for (int w = 0; w < 16; w++) {
+      for (int l = 0; l < 64; l++) {
+        const int j = r0 + w * 64 + l;
+        if (j < N) cum[j] += pre;
+      }
+      pre += wt[w];
+    }
+    carry = pre;
+  }
+}
+// ancestors of systematic resampling from the inclusive sums and the draw U
+void hc_mcl_ancestors(const uint64_t* cum, const uint64_t* q, int N, uint32_t U, int32_t* anc) {
+  int last = 0;
+  for (int j = 0; j < N; j++)
+    if (q[j] > 0) last = j;
+  for (int i = 0; i < N; i++) anc[i] = mk::mcl::ancestor(cum, N, U, i, last);
+}
+// the exact comparison c N 2^32 > (U + i 2^32) S on its own
+int hc_mcl_past(uint64_t c, int N, uint32_t U, int i, uint64_t S) { return mk::mcl::past(c, N, U, i, S) ? 1 : 0; }
+uint64_t hc_mcl_rng_next(uint64_t s) { return mk::mcl::rng_next(s); }
+
+// One step's bookkeeping on given (sum, n) inputs (mk_mcl.h step_seq): T (N x
+// 16 row-major) and L in / out; flags4 = lost, resampled, n_valid, best;
+// ess_err2 = ess, best_error; the estimate as T_mean16 and cov36 (zeros when
+// lost); E, Lnew (the log-weights before any reset) nullable
+void hc_mcl_step(const int64_t* sums, const int32_t* counts, int N, int C, double* T, double* L, double tau,
+                 double resample_frac, int32_t min_projections, uint32_t U, uint64_t* q, uint64_t* cum, int32_t* anc,
+                 int32_t* flags4, uint64_t* S, double* ess_err2, double* T_mean16, double* cov36, double* E,
+                 double* Lnew) {
+  std::vector<mk::Xf> X(N);
+  std::vector<long long> s((size_t)N * C);
+  for (size_t k = 0; k < s.size(); k++) s[k] = sums[k];
+  for (int j = 0; j < N; j++) X[j] = mk::track::xf_from_mat4(T + 16 * (size_t)j);
+  const mk::mcl::Outcome o = mk::mcl::step_seq(s.data(), counts, N, C, X.data(), L, tau, resample_frac, min_projections,
+                                               U, q, cum, anc, E, Lnew);
+  for (int j = 0; j < N; j++) mk::track::xf_to_mat4(X[j], T + 16 * (size_t)j);
+  flags4[0] = o.lost; flags4[1] = o.resampled; flags4[2] = o.n_valid; flags4[3] = o.best;
+  *S = o.S;
+  ess_err2[0] = o.ess;
+  ess_err2[1] = o.best_error;
+  if (o.lost) {
+    std::memset(T_mean16, 0, sizeof(double) * 16);
+    std::memset(cov36, 0, sizeof(double) * 36);
+  } else {
+    mk::track::xf_to_mat4(o.mean, T_mean16);
+    std::memcpy(cov36, o.cov, sizeof(double) * 36);
+  }
 }
 
 }  // extern "C"

@@ -134,15 +134,20 @@ __global__ __launch_bounds__(64) void k_track_particles(TrackArgs a, int call) {
 // int32 accumulators of wave_sums_screen_t: a slice is at most 64 x
 // kScrUnroll landmarks (static_assert below), one trip, <= kScrUnroll
 // landmarks per lane.
+// The block's work as a function of where its poses and sums lie: frame f,
+// camera `cam` of C, particles [chunk * kPP, ...) of np, task (particle j,
+// camera) at index t0 + j * C + cam of c2w / pf / sums / cnt. Shared with
+// k_mcl_score (mcl_impl.hip), whose particle set is one "rig" of up to 4096.
 template <int NT, int SPLIT>
-__global__ __launch_bounds__(NT) void k_track_score(const FrameDesc* __restrict__ frames,
-                                                    const uint32_t* __restrict__ mbits, size_t bstride, Landmarks lmk,
-                                                    TrackArgs a, int pass, int np) {
-  const int chunk = blockIdx.x, cam = blockIdx.y, rig = blockIdx.z;
+__device__ __forceinline__ void track_score_block(const FrameDesc* __restrict__ frames,
+                                                  const uint32_t* __restrict__ mbits, size_t bstride,
+                                                  const Landmarks& lmk, const Xf* __restrict__ c2w,
+                                                  const PoseF* __restrict__ pf, long long* __restrict__ sums,
+                                                  int32_t* __restrict__ cnt, size_t t0, int C, int f, int cam,
+                                                  int chunk, int np) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   constexpr int kW = NT / 64, kPP = kW / SPLIT;  // particles per block (one task per wave)
   static_assert(kW % SPLIT == 0 && kPP >= 1 && 64 * kScrUnroll * SPLIT >= 768, "one register trip per slice");
-  const int f = rig * a.C + cam;
   const FrameDesc fd = frames[f];
   const int W = fd.w, H = fd.h;
   const int nl = lmk.nw + lmk.nr + lmk.ng;
@@ -154,12 +159,11 @@ __global__ __launch_bounds__(NT) void k_track_score(const FrameDesc* __restrict_
   __shared__ uint32_t uqe[kPfQueue];
   __shared__ int32_t uqn;
   const int j0 = chunk * kPP, nj = max(0, min(kPP, np - j0));
-  const size_t t0 = (size_t)pass * a.pass_tasks + (size_t)rig * a.P * a.C;
   for (int i = tid; i < nl; i += NT) lmf[i] = lmk.xyzf[i];
   if (tid < nj) {
-    const size_t t = t0 + (size_t)(j0 + tid) * a.C + cam;
-    Pc[tid] = a.c2w[t];
-    Pf[tid] = a.pf[t];
+    const size_t t = t0 + (size_t)(j0 + tid) * C + cam;
+    Pc[tid] = c2w[t];
+    Pf[tid] = pf[t];
     Ps[tid] = 0;
     Pn[tid] = 0;
   }
@@ -190,10 +194,19 @@ __global__ __launch_bounds__(NT) void k_track_score(const FrameDesc* __restrict_
               });
   __syncthreads();
   if (tid < nj) {
-    const size_t t = t0 + (size_t)(j0 + tid) * a.C + cam;
-    a.sums[t] = (long long)Ps[tid];
-    a.cnt[t] = Pn[tid];
+    const size_t t = t0 + (size_t)(j0 + tid) * C + cam;
+    sums[t] = (long long)Ps[tid];
+    cnt[t] = Pn[tid];
   }
+}
+template <int NT, int SPLIT>
+__global__ __launch_bounds__(NT) void k_track_score(const FrameDesc* __restrict__ frames,
+                                                    const uint32_t* __restrict__ mbits, size_t bstride, Landmarks lmk,
+                                                    TrackArgs a, int pass, int np) {
+  const int chunk = blockIdx.x, cam = blockIdx.y, rig = blockIdx.z;
+  track_score_block<NT, SPLIT>(frames, mbits, bstride, lmk, a.c2w, a.pf, a.sums, a.cnt,
+                               (size_t)pass * a.pass_tasks + (size_t)rig * a.P * a.C, a.C, rig * a.C + cam, cam, chunk,
+                               np);
 }
 constexpr int kTrackPP = (kPfThreads / 64) / kPfSplit;  // k_track_score's particles per block
 
