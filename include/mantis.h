@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MANTIS_ABI_VERSION 4
+#define MANTIS_ABI_VERSION 5
 
 typedef enum mantis_status {
   MANTIS_OK = 0,
@@ -558,6 +558,75 @@ mantis_status mantis_mcl_get_record(void* ctx, double* T_w_b_pred, double* c2w, 
                                     int32_t* ancestors, int32_t* n_particles, int32_t* n_cams);
 /* Drop the filter (the next step needs an init); draws nothing. */
 mantis_status mantis_mcl_reset(void* ctx);
+
+/* ------------------------------- Monte Carlo localization: the modes (ABI 5) */
+/* The floor grid is periodic: until a coloured border comes into view the
+ * posterior has one mode per lattice cell and heading, and the step's mean of
+ * a set that spans several of them is not a pose. These calls seed the set
+ * over the lattice, read it back as one estimate per cell, and commit to one.
+ * None of them draws beyond what is said, and mantis_mcl_step is unchanged.
+ *  Key of a pose T against the anchor A (g = config.grid_spacing): ix =
+ *     (int)floor((T.t[0] - A.t[0]) / g + 0.5), iy likewise from t[1]; the yaw
+ *     quadrant k from the base x-axes projected on the world's xy plane, h =
+ *     (T.R[0][0], T.R[1][0]), a = A's: c = h . a, s = a0 h1 - a1 h0; |c| >=
+ *     |s|: k = c >= 0 ? 0 : 2; otherwise k = s > 0 ? 1 : 3 (c = s = 0: 0).
+ *     |ix|, |iy| <= 7 is in range: bin = ((iy + 7) 15 + (ix + 7)) 4 + k, 900
+ *     bins; everything else is the one bin "outside", counted, never a mode.
+ *  Anchor: particle `best` of the last step's predicted set.
+ *  Per bin, over the particles with q_j > 0: W = sum q_j (uint64, exact in any
+ *     order), n = their number, the heaviest particle (the first on ties).
+ *  Mode order: the non-empty in-range bins by W descending, then bin ascending.
+ *  Per mode, the step's estimate (5. above) restricted to the bin with w_j =
+ *     q_j / W: moments about the bin's heaviest particle, that particle's own
+ *     basis when n = 1, covariance about the mean; share = W / S; best_error =
+ *     the pooled error of the bin's heaviest particle. */
+typedef struct mantis_mcl_mode {
+  int32_t ix, iy, yaw_quadrant; /* the key against the anchor */
+  int32_t n, best, pad;         /* particles with q > 0 in the bin; the heaviest (-1: an empty record) */
+  uint64_t weight;              /* W */
+  double share, best_error;     /* W / S; E of particle best (0 / DBL_MAX in an empty record) */
+  double T_w_b[16];             /* the bin's estimate, row-major (zeros in an empty record) */
+  double covariance[36];
+} mantis_mcl_mode;
+/* The tag shares the call's name: write `struct mantis_mcl_modes`. */
+struct mantis_mcl_modes {
+  int32_t status, n_modes;      /* records filled: min(max_modes, n_cells) */
+  int32_t n_cells, n_outside;   /* non-empty in-range bins; particles with q > 0 outside */
+  uint64_t weight_sum, outside_weight; /* S; the part of it outside */
+  double anchor_T_w_b[16];      /* row-major (zeros after a lost step) */
+  mantis_mcl_mode mode[8];      /* in mode order; empty records from n_modes on */
+};
+/* sizeof(mantis_mcl_mode), sizeof(struct mantis_mcl_modes) (host only) */
+void mantis_mcl_modes_sizes(int32_t* mode_bytes, int32_t* modes_bytes);
+
+/* mantis_mcl_init over a (2 cells_x + 1) x (2 cells_y + 1) lattice of the
+ * grid: the same N x 6 gaussians in the same order, particle j = T_w_b_mean *
+ * rand_j as there, then t[0] + (double)ix * g and t[1] + (double)iy * g with
+ * site s = j % n_sites, ix = s % (2 cells_x + 1) - cells_x, iy = s / (2
+ * cells_x + 1) - cells_y. cells 0, 0 is mantis_mcl_init. Yaw alternatives are
+ * not seeded (mantis_mcl_init_particles takes any set; the keys still tell
+ * them apart). MANTIS_ERR_ARG as mantis_mcl_init, and: cells_x / cells_y
+ * outside 0..7, n_particles < n_sites. */
+mantis_status mantis_mcl_init_lattice(void* ctx, const double* T_w_b_mean, double sigma_rot0, double sigma_t0,
+                                      int32_t cells_x, int32_t cells_y, const mantis_mcl_params* p);
+/* The modes of the last step, from what it left in HBM (predicted poses, q,
+ * sums and counts; record = 0 or 1): the first min(max_modes, n_cells) of the
+ * mode order, max_modes 1..8. One launch, one copy back. After a lost step:
+ * MANTIS_OK, n_modes = 0. MANTIS_ERR_STATE: no step since the last init or
+ * reset. MANTIS_ERR_ARG: max_modes out of range, out NULL. Changes nothing in
+ * the filter. */
+mantis_status mantis_mcl_modes(void* ctx, int32_t max_modes, struct mantis_mcl_modes* out);
+/* Commit to mode mode_index of the last mantis_mcl_modes call: every particle
+ * of the current set (the resampled one if the step resampled) whose key
+ * against the same anchor differs from the mode's gets L = -inf, the others
+ * keep their L, and the context's prior pose becomes the mode's T_w_b. A
+ * dropped particle stays dropped until a resampling replaces it: the next
+ * step's ess falls and its resampling repopulates the set from the kept mode.
+ * MANTIS_ERR_STATE: no mantis_mcl_modes call since the last step, or no
+ * particle of the current set lies in the mode (a light mode may leave no
+ * offspring in a resampling) -- then nothing changes. MANTIS_ERR_ARG:
+ * mode_index not below n_modes. */
+mantis_status mantis_mcl_select_mode(void* ctx, int32_t mode_index);
 
 #ifdef __cplusplus
 }

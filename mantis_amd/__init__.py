@@ -85,6 +85,18 @@ class MantisMclResult(C.Structure):
                 ("U", C.c_uint32), ("pad", C.c_uint32), ("rng_state_after", C.c_uint64)]
 
 
+class MantisMclMode(C.Structure):
+    _fields_ = [("ix", C.c_int32), ("iy", C.c_int32), ("yaw_quadrant", C.c_int32), ("n", C.c_int32),
+                ("best", C.c_int32), ("pad", C.c_int32), ("weight", C.c_uint64), ("share", C.c_double),
+                ("best_error", C.c_double), ("T_w_b", C.c_double * 16), ("covariance", C.c_double * 36)]
+
+
+class MantisMclModes(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_modes", C.c_int32), ("n_cells", C.c_int32), ("n_outside", C.c_int32),
+                ("weight_sum", C.c_uint64), ("outside_weight", C.c_uint64), ("anchor_T_w_b", C.c_double * 16),
+                ("mode", MantisMclMode * 8)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -197,6 +209,11 @@ _SIGS = {
     "mantis_mcl_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "mantis_mcl_get_record": (C.c_int, [C.c_void_p] + [C.c_void_p] * 9 + [C.POINTER(C.c_int32)] * 2),
     "mantis_mcl_reset": (C.c_int, [C.c_void_p]),
+    "mantis_mcl_modes_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_mcl_init_lattice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                          C.POINTER(MantisMclParams)]),
+    "mantis_mcl_modes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MantisMclModes)]),
+    "mantis_mcl_select_mode": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 
@@ -544,6 +561,25 @@ class Mantis:
 
     def mcl_reset(self):
         self._chk(lib().mantis_mcl_reset(self.h), "mcl_reset")
+
+    def mcl_init_lattice(self, T_mean, sigma_rot0, sigma_t0, cells_x, cells_y, **params):
+        """mantis_mcl_init_lattice: mcl_init's draws spread over the (2 cells_x
+        + 1) x (2 cells_y + 1) lattice of the floor grid around T_mean."""
+        T = np.ascontiguousarray(T_mean, np.float64).reshape(16)
+        p = self.mcl_params(**params)
+        self._chk(lib().mantis_mcl_init_lattice(self.h, T.ctypes.data, sigma_rot0, sigma_t0, cells_x, cells_y,
+                                                C.byref(p)), "mcl_init_lattice")
+
+    def mcl_modes(self, max_modes=8):
+        """mantis_mcl_modes: the last step's set as one estimate per lattice
+        cell and yaw quadrant, heaviest first (MantisMclModes)."""
+        out = MantisMclModes()
+        self._chk(lib().mantis_mcl_modes(self.h, max_modes, C.byref(out)), "mcl_modes")
+        return out
+
+    def mcl_select_mode(self, k):
+        """mantis_mcl_select_mode: keep mode k of the last mcl_modes call."""
+        self._chk(lib().mantis_mcl_select_mode(self.h, k), "mcl_select_mode")
 
     def process_sharded(self, images, rigs, cam_index, cams_per_rig):
         """Camera-sharded rig call (mantis_process_rig_sharded): images are this

@@ -317,6 +317,11 @@ struct Ctx {
     void *d_res = nullptr, *h_res = nullptr;  // the step's result record; pinned
     bool has_record = false;  // a step has run since the init
     int rec_C = 0, rec_pred = 0;  // its cameras; which of d_T holds its predicted poses
+    // the modes of the last step (mcl_modes_impl.hip): the record and, behind it, select_mode's kept count; pinned
+    void *d_modes = nullptr, *h_modes = nullptr;
+    bool has_modes = false;  // mantis_mcl_modes has run since the last step
+    struct mantis_mcl_modes modes;  // its answer: what mantis_mcl_select_mode commits to
+    double modes_g = 0;             // the grid spacing its keys were taken with
   } mcl;
 };
 
@@ -1360,12 +1365,12 @@ mantis_status mantis_destroy(void* ctx) {
   for (void* p : tptrs)
     if (p) (void)hipFree(p);
   void* mptrs[] = {c->mcl.d_T[0], c->mcl.d_T[1], c->mcl.d_L, c->mcl.d_Lprev, c->mcl.d_q, c->mcl.d_cum, c->mcl.d_anc,
-                   c->mcl.d_in, c->mcl.d_c2w, c->mcl.d_pf, c->mcl.d_sums, c->mcl.d_cnt, c->mcl.d_res};
+                   c->mcl.d_in, c->mcl.d_c2w, c->mcl.d_pf, c->mcl.d_sums, c->mcl.d_cnt, c->mcl.d_res, c->mcl.d_modes};
   for (void* p : mptrs)
     if (p) (void)hipFree(p);
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
-                   c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res};
+                   c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes};
   for (void* p : hptrs)
     if (p) (void)hipHostFree(p);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -2211,4 +2216,5 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "markov_impl.hip"
 #include "track_impl.hip"
 #include "mcl_impl.hip"
+#include "mcl_modes_impl.hip"
 #include "ros_wire.h"

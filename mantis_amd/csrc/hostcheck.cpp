@@ -17,6 +17,7 @@ static int g_jacobi_ff = 1;
 #include "mk_gn.h"
 #include "mk_math.h"
 #include "mk_mcl.h"
+#include "mk_mcl_modes.h"
 #include "mk_rpp.h"
 #include "mk_screen.h"
 #include "mk_shard.h"
@@ -488,6 +489,22 @@ void hc_mcl_step(const int64_t* sums, const int32_t* counts, int N, int C, doubl
     mk::track::xf_to_mat4(o.mean, T_mean16);
     std::memcpy(cov36, o.cov, sizeof(double) * 36);
   }
+}
+
+// The modes of the set (mk_mcl_modes.h): the rules k_mcl_modes / k_mcl_keep run.
+// key4 = ix, iy, k, bin of pose T against the anchor A (row-major 4x4 each)
+void hc_mcl_cell_key(const double* T, const double* A, double g, int32_t* key4) {
+  key4[3] = mk::mcl::cell_key(mk::track::xf_from_mat4(T), mk::track::xf_from_mat4(A), g, key4, key4 + 1, key4 + 2);
+}
+void hc_mcl_lattice_site(int s, int cx, int cy, int32_t* ixy2) { mk::mcl::lattice_site(s, cx, cy, ixy2, ixy2 + 1); }
+// modes_seq on T (N x 16 row-major), q, sums / counts (N x C); out: a struct mantis_mcl_modes
+void hc_mcl_modes(const double* T, const uint64_t* q, const int64_t* sums, const int32_t* counts, int N, int C, int best,
+                  double g, int max_modes, void* out) {
+  std::vector<mk::Xf> X(N);
+  std::vector<long long> s((size_t)N * C);
+  for (size_t k = 0; k < s.size(); k++) s[k] = sums[k];
+  for (int j = 0; j < N; j++) X[j] = mk::track::xf_from_mat4(T + 16 * (size_t)j);
+  mk::mcl::modes_seq(X.data(), q, s.data(), counts, N, C, best, g, max_modes, (mk::mcl::Modes*)out);
 }
 
 }  // extern "C"

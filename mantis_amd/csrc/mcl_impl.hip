@@ -305,6 +305,7 @@ mantis_status mcl_workspace(Ctx* c, int N) {
   HIP_OK(hipStreamSynchronize(c->s));  // nothing of an earlier step still reads what is freed
   m.cap = 0;
   m.live = false;
+  m.has_record = m.has_modes = false;
   const size_t n = (size_t)N, tasks = n * mk::track::kMaxCams;
   const size_t in_bytes = sizeof(Xf) * (mk::track::kMaxCams + 1) + sizeof(float) * n * 6;
   if (m.h_in) (void)hipHostFree(m.h_in);
@@ -334,6 +335,7 @@ mantis_status mcl_upload(Ctx* c, const std::vector<Xf>& T, const mantis_mcl_para
   m.N = N;
   m.cur = 0;
   m.has_record = false;
+  m.has_modes = false;
   m.live = true;
   return MANTIS_OK;
 }
@@ -402,6 +404,7 @@ mantis_status mantis_mcl_reset(void* ctx) {
   if (!c) return MANTIS_ERR_ARG;
   c->mcl.live = false;
   c->mcl.has_record = false;
+  c->mcl.has_modes = false;
   return MANTIS_OK;
 }
 
@@ -460,6 +463,7 @@ mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cam
   const size_t in_bytes = sizeof(Xf) * (mk::track::kMaxCams + 1) + sizeof(float) * (size_t)N * 6;
 
   m.has_record = false;
+  m.has_modes = false;  // the modes are the last step's
   int W, H;
   mantis_status st = stage_frames(c, cams, C, W, H);
   if (st != MANTIS_OK) return st;
