@@ -628,6 +628,77 @@ mantis_status mantis_mcl_modes(void* ctx, int32_t max_modes, struct mantis_mcl_m
  * mode_index not below n_modes. */
 mantis_status mantis_mcl_select_mode(void* ctx, int32_t mode_index);
 
+/* ---------------- Monte Carlo localization: the colour evidence (additions) */
+/* The step's scorer is the fast WHITE evaluator, which cannot tell one cell of
+ * the floor grid from the next. These calls let the set also weigh the green
+ * border with the reference's slow COLOR evaluator (computePointError(...,
+ * GREEN, fast = false), HypothesisEvaluation.h:233-266) on the raw frames.
+ * They only add: with enable = 0 a step is the step above, bit for bit, and
+ * the ABI version stays 5 (look the entry points up by name, or call
+ * mantis_mcl_color_sizes).
+ *  Colour sums of (particle j, camera c), c2w as in 3. above: every green
+ *     landmark in map order, projected exactly in FP64, is scored iff z > 0 and
+ *     inFrame(u, v); its window sum is the integer sum over ox, oy in -5..4 of
+ *     (b - 50)^2 + (g - 255)^2 + (r - 85)^2 at linear offset cvRound(v + oy) W +
+ *     cvRound(u + ox) of the raw BGR frame, an offset outside [0, W H) reading
+ *     0, 0, 0. csum (int64) = the sum of the window sums, cn (int32) = the
+ *     number of scored landmarks.
+ *  Pooled colour error: Ec_j = (double)sum_c csum / ((double)sum_c cn * 100.0 *
+ *     1.1), defined when sum_c cn >= min_color_projections; DBL_MAX otherwise.
+ *  Charge: charge_j = Ec_j / color_tau when defined, color_miss / color_tau
+ *     otherwise (a particle must not win by seeing no green at all).
+ *  enable = 2: step 4. becomes L_j <- (L_j - E_j / tau) - charge_j for the
+ *     valid particles, in that operation order; validity (by the WHITE counts
+ *     alone) and everything after are unchanged, a lost step leaves L as it was.
+ *  enable = 1: the sums, Ec and the charge are computed and kept, the weights
+ *     are those of enable = 0.
+ *  A map without green landmarks: every cn = 0, every Ec = DBL_MAX, every
+ *     charge = color_miss / color_tau.
+ * One more launch per step (5 instead of 4) while enable >= 1.
+ * Defaults, measured with the CPU oracle over the 32 four-camera 720p
+ * synthetic rigs of tools/mcl_latency.py (tools/mcl_color_defaults.py), among
+ * the rigs with >= 10 green landmarks in view at the truth (all 32; 120 .. 148
+ * of the 4 x 37 are in view): color_miss = the median Ec(truth) = 15447.3
+ * (quartiles 14224.9 / 16948.3, range 11028.7 .. 18415.8); color_tau = the
+ * median of Ec(truth moved one cell, 0.32 m, along world y) - Ec(truth) =
+ * 33379.0 (quartiles 30605.8 / 36813.5, range 25760.0 .. 44890.9; positive on
+ * every rig), so that a particle one cell off keeps about 1/e per step from
+ * colour alone. DESIGN.md 4d. */
+#define MANTIS_MCL_COLOR_MISS_DEFAULT 15447.3
+#define MANTIS_MCL_COLOR_TAU_DEFAULT 33379.0
+typedef struct mantis_mcl_color_params {
+  int32_t struct_size;            /* sizeof(mantis_mcl_color_params) */
+  int32_t enable;                 /* 0 = off; 1 = score and record only; 2 = score and fold into L */
+  double color_tau;               /* > 0, finite */
+  double color_miss;              /* >= 0, finite: Ec of a particle with too few green landmarks in view */
+  int32_t min_color_projections;  /* >= 1 */
+  int32_t pad;
+} mantis_mcl_color_params;
+/* 0 / MANTIS_MCL_COLOR_TAU_DEFAULT / MANTIS_MCL_COLOR_MISS_DEFAULT / 10 */
+void mantis_default_mcl_color_params(mantis_mcl_color_params* p);
+/* sizeof(mantis_mcl_color_params) (host only) */
+void mantis_mcl_color_sizes(int32_t* params_bytes);
+/* Legal at any time after mantis_create; persists across inits and resets,
+ * applies from the next step, draws nothing. MANTIS_ERR_ARG (nothing changes):
+ * a null pointer, struct_size, enable outside 0..2, color_tau not finite and
+ * > 0, color_miss not finite and >= 0, min_color_projections < 1. */
+mantis_status mantis_mcl_set_color(void* ctx, const mantis_mcl_color_params* p);
+/* The last step's colour record, whatever params.record says, each pointer
+ * nullable: csums / ccounts (N x C) of the predicted set, Ec (N, DBL_MAX
+ * where undefined) and charge (N); *n_particles = N, *n_cams = C. The arrays
+ * stay in HBM until asked for. MANTIS_ERR_STATE: no step since the last init
+ * or reset, or that step ran with enable = 0. */
+mantis_status mantis_mcl_get_color_record(void* ctx, int64_t* csums, int32_t* ccounts, double* Ec, double* charge,
+                                          int32_t* n_particles, int32_t* n_cams);
+/* For each mode of the last mantis_mcl_modes call, Ec and sum_c cn of the
+ * mode's heaviest particle (mode[i].best), 8 entries each; DBL_MAX / 0 in
+ * empty records. Reads back, launches nothing, changes nothing. With enable =
+ * 1 a server chooses the mode by colour and commits with
+ * mantis_mcl_select_mode. MANTIS_ERR_STATE: no mantis_mcl_modes call since
+ * the last step, or that step ran with enable = 0. MANTIS_ERR_ARG: a null
+ * pointer. */
+mantis_status mantis_mcl_modes_color(void* ctx, double* color_error /*8*/, int32_t* color_n /*8*/);
+
 #ifdef __cplusplus
 }
 #endif

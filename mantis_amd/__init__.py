@@ -97,6 +97,11 @@ class MantisMclModes(C.Structure):
                 ("mode", MantisMclMode * 8)]
 
 
+class MantisMclColorParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("enable", C.c_int32), ("color_tau", C.c_double),
+                ("color_miss", C.c_double), ("min_color_projections", C.c_int32), ("pad", C.c_int32)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -214,6 +219,11 @@ _SIGS = {
                                           C.POINTER(MantisMclParams)]),
     "mantis_mcl_modes": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MantisMclModes)]),
     "mantis_mcl_select_mode": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mantis_default_mcl_color_params": (None, [C.POINTER(MantisMclColorParams)]),
+    "mantis_mcl_color_sizes": (None, [C.POINTER(C.c_int32)]),
+    "mantis_mcl_set_color": (C.c_int, [C.c_void_p, C.POINTER(MantisMclColorParams)]),
+    "mantis_mcl_get_color_record": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.POINTER(C.c_int32)] * 2),
+    "mantis_mcl_modes_color": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -580,6 +590,42 @@ class Mantis:
     def mcl_select_mode(self, k):
         """mantis_mcl_select_mode: keep mode k of the last mcl_modes call."""
         self._chk(lib().mantis_mcl_select_mode(self.h, k), "mcl_select_mode")
+
+    def mcl_color_params(self, **params):
+        """mantis_default_mcl_color_params, then the overrides."""
+        p = MantisMclColorParams()
+        lib().mantis_default_mcl_color_params(C.byref(p))
+        for k, v in params.items():
+            if k not in dict(MantisMclColorParams._fields_) or k == "struct_size":
+                raise TypeError(f"mcl colour: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def mcl_set_color(self, enable, **params):
+        """mantis_mcl_set_color: 0 = off, 1 = score and record the green
+        border's COLOR evidence, 2 = also fold it into the log-weights."""
+        p = self.mcl_color_params(enable=enable, **params)
+        self._chk(lib().mantis_mcl_set_color(self.h, C.byref(p)), "mcl_set_color")
+
+    def mcl_color_record(self):
+        """mantis_mcl_get_color_record: the last step's colour record as a
+        dict: csums [N, C] int64, ccounts [N, C] int32, Ec / charge [N]."""
+        n, cn = C.c_int32(), C.c_int32()
+        self._chk(lib().mantis_mcl_get_color_record(self.h, None, None, None, None, C.byref(n), C.byref(cn)),
+                  "mcl_get_color_record")
+        N, Cn = n.value, cn.value
+        r = {"csums": np.zeros((N, Cn), np.int64), "ccounts": np.zeros((N, Cn), np.int32), "Ec": np.zeros(N),
+             "charge": np.zeros(N)}
+        self._chk(lib().mantis_mcl_get_color_record(self.h, *[a.ctypes.data for a in r.values()], C.byref(n),
+                                                    C.byref(cn)), "mcl_get_color_record")
+        return r
+
+    def mcl_modes_color(self):
+        """mantis_mcl_modes_color: (Ec [8], pooled green count [8]) of the
+        heaviest particle of each mode of the last mcl_modes call."""
+        e, n = np.zeros(8), np.zeros(8, np.int32)
+        self._chk(lib().mantis_mcl_modes_color(self.h, e.ctypes.data, n.ctypes.data), "mcl_modes_color")
+        return e, n
 
     def process_sharded(self, images, rigs, cam_index, cams_per_rig):
         """Camera-sharded rig call (mantis_process_rig_sharded): images are this

@@ -322,6 +322,14 @@ struct Ctx {
     bool has_modes = false;  // mantis_mcl_modes has run since the last step
     struct mantis_mcl_modes modes;  // its answer: what mantis_mcl_select_mode commits to
     double modes_g = 0;             // the grid spacing its keys were taken with
+    // the colour evidence (mcl_color_impl.hip): what mantis_mcl_set_color left (enable 0 until then), the
+    // (csum, cn) of the last step with colour on, N x C, its pooled Ec and charge, N
+    mantis_mcl_color_params color{};
+    long long* d_csums = nullptr;
+    int32_t* d_ccnt = nullptr;
+    double *d_Ec = nullptr, *d_charge = nullptr;
+    int color_cap = 0;                      // particles the colour buffers hold
+    int rec_color = 0, rec_color_min = 0;   // the last step's enable and min_color_projections
   } mcl;
 };
 
@@ -1365,7 +1373,8 @@ mantis_status mantis_destroy(void* ctx) {
   for (void* p : tptrs)
     if (p) (void)hipFree(p);
   void* mptrs[] = {c->mcl.d_T[0], c->mcl.d_T[1], c->mcl.d_L, c->mcl.d_Lprev, c->mcl.d_q, c->mcl.d_cum, c->mcl.d_anc,
-                   c->mcl.d_in, c->mcl.d_c2w, c->mcl.d_pf, c->mcl.d_sums, c->mcl.d_cnt, c->mcl.d_res, c->mcl.d_modes};
+                   c->mcl.d_in, c->mcl.d_c2w, c->mcl.d_pf, c->mcl.d_sums, c->mcl.d_cnt, c->mcl.d_res, c->mcl.d_modes,
+                   c->mcl.d_csums, c->mcl.d_ccnt, c->mcl.d_Ec, c->mcl.d_charge};
   for (void* p : mptrs)
     if (p) (void)hipFree(p);
   for (void* p : c->user_allocs) (void)hipFree(p);
@@ -2217,4 +2226,5 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "track_impl.hip"
 #include "mcl_impl.hip"
 #include "mcl_modes_impl.hip"
+#include "mcl_color_impl.hip"
 #include "ros_wire.h"

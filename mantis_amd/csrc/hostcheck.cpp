@@ -17,6 +17,7 @@ static int g_jacobi_ff = 1;
 #include "mk_gn.h"
 #include "mk_math.h"
 #include "mk_mcl.h"
+#include "mk_mcl_color.h"
 #include "mk_mcl_modes.h"
 #include "mk_rpp.h"
 #include "mk_screen.h"
@@ -505,6 +506,40 @@ void hc_mcl_modes(const double* T, const uint64_t* q, const int64_t* sums, const
   for (size_t k = 0; k < s.size(); k++) s[k] = sums[k];
   for (int j = 0; j < N; j++) X[j] = mk::track::xf_from_mat4(T + 16 * (size_t)j);
   mk::mcl::modes_seq(X.data(), q, s.data(), counts, N, C, best, g, max_modes, (mk::mcl::Modes*)out);
+}
+
+// The colour evidence (mk_mcl_color.h): the rules k_mcl_color / k_mcl_weight run.
+// the window sum of a landmark at (u, v) on the raw BGR frame (W x H, stride 3 W)
+int32_t hc_mcl_color_window(const uint8_t* bgr, int W, int H, double u, double v) {
+  return mk::mcl::color_window_sum(bgr, W, H, u, v);
+}
+// (csum, cn) of n poses c2w (12 each: R row-major | t) over the ng green landmarks
+void hc_mcl_color_sums(const double* c2w, int n, const double* green, int ng, const double* K, const double* D,
+                       const uint8_t* bgr, int W, int H, int64_t* csum, int32_t* cn) {
+  mk::Cam cm{(double)(float)K[0], (double)(float)K[4], (double)(float)K[2], (double)(float)K[5], {D[0], D[1], D[2], D[3]}};
+  for (int i = 0; i < n; i++) {
+    mk::Xf T;
+    for (int k = 0; k < 12; k++) (k < 9 ? T.R[k] : T.t[k - 9]) = c2w[12 * i + k];
+    long long s;
+    mk::mcl::color_sums(T, green, ng, cm, bgr, W, H, &s, &cn[i]);
+    csum[i] = s;
+  }
+}
+// pooled Ec (DBL_MAX where undefined), the pooled count and the charge of N particles from csums / cns (N x C)
+void hc_mcl_color_charge(const int64_t* csums, const int32_t* cns, int N, int C, int32_t min_color_projections,
+                         double color_miss, double color_tau, double* Ec, int32_t* n_out, double* charge) {
+  std::vector<long long> s(C > 0 ? C : 1);
+  for (int j = 0; j < N; j++) {
+    for (int c = 0; c < C; c++) s[c] = csums[(size_t)j * C + c];
+    Ec[j] = mk::mcl::color_pool(s.data(), cns + (size_t)j * C, C, min_color_projections, &n_out[j]);
+    charge[j] = mk::mcl::color_charge(Ec[j], color_miss, color_tau);
+  }
+}
+// L <- (L - E / tau) - charge or -inf
+void hc_mcl_color_fold(const double* L, const double* E, const int32_t* n_proj, const double* charge, int N, double tau,
+                       int32_t min_projections, double* L_out) {
+  for (int j = 0; j < N; j++)
+    L_out[j] = mk::mcl::log_weight_color(L[j], E[j], n_proj[j], min_projections, tau, charge[j]);
 }
 
 }  // extern "C"

@@ -5,13 +5,15 @@
 // (shared with the host build of the tests).
 //
 // Device work of one step, all on the context stream: the image stages up to
-// the cleanImageByEdge bit plane (run_image_stages), then 4 launches:
+// the cleanImageByEdge bit plane (run_image_stages), then 4 launches (5 with
+// the colour evidence on: k_mcl_color, mcl_color_impl.hip, after k_mcl_score):
 //   k_mcl_predict    one lane per particle: T_j <- T_j * Delta * rand_j, and per
 //                    camera the FP64 c2w and its FP32 screen pose
 //   k_mcl_score      grid (particle chunk, camera): track_score_block, the very
 //                    body of k_track_score (track_impl.hip); each (particle,
 //                    camera) owned by one block, (sum, n) written with one store
-//   k_mcl_weight     one block of 1024: pool, validity, L, Lmax, q, the integer
+//   k_mcl_weight     one block of 1024: pool, validity, L (less the colour charge
+//                    in the instantiation that folds it), Lmax, q, the integer
 //                    scan (c_j, S), best, ess, the estimate, the covariance,
 //                    the ancestors when resampling, the result record
 //   k_mcl_resample   gathers the poses by ancestor into the other buffer of the
@@ -20,6 +22,7 @@
 // Every hand-off between blocks is a kernel boundary: no last-block counter,
 // no polled flag, no hipGraph capture.
 #include "mk_mcl.h"
+#include "mk_mcl_color.h"
 
 namespace mk {
 
@@ -39,6 +42,7 @@ struct MclArgs {
   long long* sums;     // N x C
   int32_t* cnt;
   mantis_mcl_result* res;
+  const double* charge;  // N: the colour charge k_mcl_weight<true> folds into L (null otherwise)
   int32_t N, C, min_projections, has_motion;
   uint32_t U;
   double sigma_rot, sigma_t, tau, resample_frac;
@@ -98,7 +102,10 @@ __device__ inline double mcl_block_max(double v, double (*sh)[kMclWT / 64]) {
   return t;
 }
 
-// One block. Particle j = round * 1024 + tid, at most 4 rounds.
+// One block. Particle j = round * 1024 + tid, at most 4 rounds. COLOR: L also
+// pays a.charge (mk_mcl_color.h); the step without colour runs the other
+// instantiation, whose arithmetic and registers are those it always had.
+template <bool COLOR>
 __global__ __launch_bounds__(kMclWT) void k_mcl_weight(MclArgs a) {
   constexpr int NT = kMclWT, kW = NT / 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -122,7 +129,8 @@ __global__ __launch_bounds__(kMclWT) void k_mcl_weight(MclArgs a) {
       E[r] = track::pool(a.sums + (size_t)j * C, a.cnt + (size_t)j * C, C, &n);
       const double Lp = a.L[j];
       a.Lprev[j] = Lp;
-      Ln[r] = mcl::log_weight(Lp, E[r], n, a.min_projections, a.tau);
+      if (COLOR && a.charge) Ln[r] = mcl::log_weight_color(Lp, E[r], n, a.min_projections, a.tau, a.charge[j]);
+      else Ln[r] = mcl::log_weight(Lp, E[r], n, a.min_projections, a.tau);
       lmax = fmax(lmax, Ln[r]);
       a.anc[j] = -1;
     }
@@ -340,6 +348,10 @@ mantis_status mcl_upload(Ctx* c, const std::vector<Xf>& T, const mantis_mcl_para
   return MANTIS_OK;
 }
 
+// the colour evidence of a step (mcl_color_impl.hip)
+mantis_status mcl_color_workspace(Ctx* c);
+mantis_status mcl_color_stage(Ctx* c, const mk::MclArgs& s);
+
 }  // namespace
 
 extern "C" {
@@ -462,6 +474,9 @@ mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cam
   const uint32_t U = (uint32_t)s;
   const size_t in_bytes = sizeof(Xf) * (mk::track::kMaxCams + 1) + sizeof(float) * (size_t)N * 6;
 
+  const int color = m.color.enable;  // as mantis_mcl_set_color left it: 0 = the step without colour
+  if (color)
+    if (mantis_status e = mcl_color_workspace(c)) return e;
   m.has_record = false;
   m.has_modes = false;  // the modes are the last step's
   int W, H;
@@ -486,6 +501,7 @@ mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cam
   a.sums = m.d_sums;
   a.cnt = m.d_cnt;
   a.res = (mantis_mcl_result*)m.d_res;
+  a.charge = color == 2 ? m.d_charge : nullptr;
   a.N = N;
   a.C = C;
   a.min_projections = m.p.min_projections;
@@ -503,7 +519,10 @@ mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cam
   mk::k_mcl_score<kPfThreads, kPfSplit><<<grid, kPfThreads, 0, c->s>>>(c->d_frames, c->d_mbits, c->bstride, lmk_of(c), a);
   HIP_OK(hipGetLastError());
   mark(c, "mcl_score/k_mcl_score");
-  mk::k_mcl_weight<<<1, mk::kMclWT, 0, c->s>>>(a);
+  if (color)
+    if (mantis_status e = mcl_color_stage(c, a)) return e;
+  if (color == 2) mk::k_mcl_weight<true><<<1, mk::kMclWT, 0, c->s>>>(a);
+  else mk::k_mcl_weight<false><<<1, mk::kMclWT, 0, c->s>>>(a);
   HIP_OK(hipGetLastError());
   mark(c, "mcl_weight/k_mcl_weight");
   mk::k_mcl_resample<<<nb, 256, 0, c->s>>>(a);
@@ -521,6 +540,8 @@ mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cam
   c->rng_state = s;
   m.rec_pred = m.cur;  // the predicted poses stay in the buffer the step found the set in
   m.rec_C = C;
+  m.rec_color = color;
+  m.rec_color_min = m.color.min_color_projections;
   m.has_record = true;
   if (r.resampled) m.cur ^= 1;
   if (mout) *mout = r;
