@@ -187,17 +187,12 @@ struct Ctx {
   // path): tiles, whose ~230 blocks per frame run at once, where the strip
   // walk of a frame is 720 dependent row steps (MANTIS_CANNY_STRIP sets both)
   int canny_small = 0;
-#ifndef MK_SHIFT_SPLIT
-#define MK_SHIFT_SPLIT 0
-#endif
-  bool shift_split = MK_SHIFT_SPLIT;
 #ifndef MK_GN_FUSED_ALL
 #define MK_GN_FUSED_ALL 1  // round 6: 29.2 / 29.3k -> 29.7 / 30.0k rig poses/s (6 contexts, A/B/A/B)
 #endif
   bool gn_fused_all = MK_GN_FUSED_ALL;  // the rig GN as one k_rig_gn_fused launch for every batch size (MANTIS_GN_FUSED)
-  bool pf_shifts = true;  // large batches: the 81 shifts at the end of k_score_pf (MANTIS_PF_SHIFTS)
   int pf_init = 1;  // large batches: k_score_init's work at the start of k_score_pf (MANTIS_PF_INIT; 2: its
-                   // per-hypothesis arrays in global scratch, as for more hypotheses than its LDS buffer takes)  // large batches: the 81 shifts in k_score_shift_part blocks (MANTIS_SHIFT_SPLIT)
+                   // per-hypothesis arrays in global scratch, as for more hypotheses than its LDS buffer takes)
   bool canny_cat = true;  // k_canny_strip<2> over the frames side by side where W % 32 == 0 (MANTIS_CANNY_CAT=0: per frame)
   bool counted = false;  // included in g_live_ctx
   bool vec_ok = false;
@@ -791,8 +786,7 @@ mantis_status run_score(Ctx* c, int n, int n_gauss, bool copy_gauss = true) {
   const bool split = c->pf_split && n <= c->fc_small_frames && c->cfg.particles <= kPfMaxParticles &&
                      c->cfg.iterations > 0;
   // large batches: k_score_init's work at the start of k_score_pf (pf_init), the
-  // 81 shifts at its end (pf_shifts), both with the frame's mask in LDS
-  const bool pf_shifts = !split && c->pf_shifts;
+  // 81 shifts at its end, both with the frame's mask in LDS
   const int pf_init = split ? 0 : c->pf_init;
   if (!pf_init) {
     k_score_init<kScoreInit><<<n, kScoreInit, 0, c->s>>>(c->d_frames, c->d_mbits, c->bstride, L, c->d_st, c->d_hyps,
@@ -817,26 +811,22 @@ mantis_status run_score(Ctx* c, int n, int n_gauss, bool copy_gauss = true) {
   } else if (ml)
     k_score_pf<kPfThreads, kPfSplit, true><<<n, kPfThreads, ml, c->s>>>(
         c->d_frames, c->d_mbits, c->bstride, L, c->d_st, c->d_gauss, c->d_res, c->d_dbg, c->d_sst, c->cfg.particles,
-        c->cfg.iterations, pf_shifts ? 1 : 0, c->cfg.grid_spacing, 9, pf_init, c->d_hyps,
-        (unsigned char*)c->d_gen);
+        c->cfg.iterations, c->cfg.grid_spacing, 9, pf_init, c->d_hyps, (unsigned char*)c->d_gen);
   else
     k_score_pf<kPfThreads, kPfSplit, false><<<n, kPfThreads, 0, c->s>>>(
         c->d_frames, c->d_mbits, c->bstride, L, c->d_st, c->d_gauss, c->d_res, c->d_dbg, c->d_sst, c->cfg.particles,
-        c->cfg.iterations, pf_shifts ? 1 : 0, c->cfg.grid_spacing, 9, pf_init, c->d_hyps,
-        (unsigned char*)c->d_gen);
+        c->cfg.iterations, c->cfg.grid_spacing, 9, pf_init, c->d_hyps, (unsigned char*)c->d_gen);
   mark(c, "score_pf_yaw/k_score_pf");
-  // the 81 shifts over several blocks per frame first (small batches; large
-  // ones with shift_split: the shift tasks in a lean kernel instead of beside
-  // k_score_final's sorting, COLOR and publishing code)
-  const bool shifts_apart = !pf_shifts && (split || c->shift_split);
-  if (shifts_apart) {
+  // small batches: the 81 shifts over several blocks per frame (large ones
+  // scored them at the end of k_score_pf)
+  if (split) {
     constexpr int spb = kScoreTail / 128;
     k_score_shift_part<kScoreTail><<<dim3((81 + spb - 1) / spb, n), kScoreTail, 0, c->s>>>(
         c->d_frames, c->d_mbits, c->bstride, L, c->d_st, c->d_sst, c->cfg.grid_spacing, 9, spb);
     mark(c, "score_pf_yaw/k_score_shift_part");
   }
-  k_score_final<kScoreTail><<<n, kScoreTail, 0, c->s>>>(c->d_frames, c->d_mbits, c->bstride, L, c->d_st, c->d_res, c->d_dbg,
-                                               c->d_sst, c->cfg.grid_spacing, 9, shifts_apart || pf_shifts);
+  k_score_final<kScoreTail><<<n, kScoreTail, 0, c->s>>>(c->d_frames, L, c->d_st, c->d_res, c->d_dbg, c->d_sst,
+                                                        c->cfg.grid_spacing, 9);
   mark(c, "score_pf_yaw/k_score_final");
   HIP_OK(hipGetLastError());
   return MANTIS_OK;
@@ -1184,8 +1174,6 @@ mantis_status mantis_create(const mantis_config* cfg_in, void** out_ctx) {
   if (const char* e = std::getenv("MANTIS_SEG_M")) c->seg_m = std::max(0, std::min(4096, std::atoi(e)));
   if (const char* e = std::getenv("MANTIS_CANNY_STRIP")) c->canny_strip = c->canny_small = std::atoi(e);
   if (const char* e = std::getenv("MANTIS_CANNY_CAT")) c->canny_cat = e[0] != '0';
-  if (const char* e = std::getenv("MANTIS_SHIFT_SPLIT")) c->shift_split = e[0] != '0';
-  if (const char* e = std::getenv("MANTIS_PF_SHIFTS")) c->pf_shifts = e[0] != '0';
   if (const char* e = std::getenv("MANTIS_GN_FUSED")) c->gn_fused_all = e[0] != '0';
   if (const char* e = std::getenv("MANTIS_PF_INIT")) c->pf_init = std::max(0, std::min(2, std::atoi(e)));
   if (const char* e = std::getenv("MANTIS_HYST_REC")) c->hyst_rec = e[0] != '0';

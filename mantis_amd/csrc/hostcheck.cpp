@@ -400,6 +400,7 @@ void hc_track_pool(const int64_t* sums, const int32_t* counts, int n_particles, 
                              &n_proj[j]);
   }
 }
+double hc_track_error_of(int64_t sum, int32_t n) { return mk::track::error_of((long long)sum, n); }
 int hc_track_pick(const double* err, int n, double cur_err) { return mk::track::pick(err, n, cur_err); }
 int hc_track_gate(double error, int32_t n_proj, int32_t min_projections, double max_error) {
   return mk::track::gate(error, n_proj, min_projections, max_error);

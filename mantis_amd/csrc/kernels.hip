@@ -22,6 +22,7 @@
 
 #include <cfloat>
 #include <cstdint>
+#include <type_traits>
 
 #include "mk_bits.h"
 #include "mk_contour.h"
@@ -30,6 +31,7 @@
 #include "mk_rpp.h"
 #include "mk_shard.h"
 #include "mk_sort.h"
+#include "mk_track.h"
 #include "mk_types.h"
 #include "synth.h"
 
@@ -4718,17 +4720,114 @@ struct WaveLms {
                           n_out);
   }
 };
-// the block recomputes the queued landmarks exactly: add(tag, term) for those
-// in frame (pose_of(tag) = the tag's FP64 c2w)
-template <class MK, class PoseOf, class Add>
-__device__ inline void block_drain(UQueue q, const double* lmd, const Cam* cmp, int W, int H, const uint8_t* bgr,
-                                   const MK& mask, const PoseOf& pose_of, const Add& add) {
-  const int n = min(*q.n, q.cap);
+
+// The block scorer: the one block-level sequence of every fast scorer. A block
+// of NT threads scores np poses of one frame: each wave takes (pose, landmark
+// slice) tasks with its slice -- wave % SPLIT of SPLIT, the only way a slice
+// is chosen -- resident in registers, lane 0 adds the wave's integer total
+// into the pose's slot, and after a barrier the whole block recomputes the
+// queued unsure landmarks exactly and adds their terms into the same slots.
+// The sums are exact integers, so the order of the adds is free.
+//   BlockScore   the frame (screen camera, W, H, bgr: fd), its exact camera,
+//                the FP64 landmarks, the mask (LDS, global bits, bytes or
+//                none: chosen once, by type), the unsure queue, the wave's slice
+//   Poses        pf(j): pose j as the FP32 screen reads it; c2w(j): the exact
+//                FP64 one. The task loop, the in-place recomputation of a wave
+//                that finds the queue full and the drain read the same source.
+//   ScoreSlots   per pose: integer error sum and count (LDS, or global scratch)
+struct ScoreSlots {
+  unsigned long long* s;
+  int32_t* n;
+};
+template <int NT, int SPLIT, class MK>
+struct BlockScore {
+  static_assert((NT / 64) % SPLIT == 0 && 64 * kScrUnroll * SPLIT >= 768, "one register trip per slice");
+  const FrameDesc& fd;
+  const Cam* cmp;
+  const double* lmd;
+  // (a reference: exact_term is not inlined and takes the mask's address; were
+  // the mask a part of this struct, the whole struct would live in scratch)
+  const MK& mask;
+  UQueue q;
+  WaveLms<kScrUnroll> wl;
+  // the wave's slice of the nl landmarks staged in lmf (LDS, visible)
+  __device__ void load(const float4* lmf, int nl) {
+    const int h = (threadIdx.x >> 6) % SPLIT;
+    wl.load(lmf, nl * h / SPLIT, nl * (h + 1) / SPLIT);
+  }
+};
+// poses staged in LDS in both forms
+struct StagedPoses {
+  const PoseF* f;
+  const Xf* c;
+  __device__ const PoseF& pf(int j) const { return f[j]; }
+  __device__ const Xf& c2w(int j) const { return c[j]; }
+};
+// The screened tasks. At entry the slots of the np poses and the queue count
+// are zero and visible to the block (zeroed before a barrier the caller has).
+template <int NT, int SPLIT, class MK, class Poses>
+__device__ __forceinline__ void block_score_tasks(const BlockScore<NT, SPLIT, MK>& b, const Poses& poses, int np,
+                                                  ScoreSlots out) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int task = __builtin_amdgcn_readfirstlane(wave); task < np * SPLIT; task += NT / 64) {
+    const int j = task / SPLIT;  // task % SPLIT == wave % SPLIT: the wave's resident slice
+    long long s;
+    int n;
+    b.wl.sums(poses.pf(j), b.fd.scam, b.fd.w, b.fd.h, b.fd.bgr, b.mask, b.q, j, &poses.c2w(j), b.lmd, b.cmp, s, n);
+    if (lane == 0) {
+      atomicAdd(&out.s[j], (unsigned long long)s);
+      atomicAdd(&out.n[j], n);
+    }
+  }
+}
+// The block recomputes the queued landmarks exactly (after a barrier behind
+// the tasks; the caller's next barrier makes the slots final).
+template <int NT, int SPLIT, class MK, class Poses>
+__device__ __forceinline__ void block_score_drain(const BlockScore<NT, SPLIT, MK>& b, const Poses& poses,
+                                                  ScoreSlots out) {
+  const int n = min(*b.q.n, b.q.cap);
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const uint32_t en = q.e[i];
+    const uint32_t en = b.q.e[i];
     const int tag = (int)(en >> 16), l = (int)(en & 0xffffu);
     int e;
-    if (exact_term(pose_of(tag), lmd + 3 * l, *cmp, W, H, bgr, mask, e)) add(tag, e);
+    if (exact_term(poses.c2w(tag), b.lmd + 3 * l, *b.cmp, b.fd.w, b.fd.h, b.fd.bgr, b.mask, e)) {
+      atomicAdd(&out.s[tag], (unsigned long long)e);
+      atomicAdd(&out.n[tag], 1);
+    }
+  }
+}
+// tasks, barrier, drain, barrier: the slots hold every pose's (sum, n)
+template <int NT, int SPLIT, class MK, class Poses>
+__device__ __forceinline__ void block_score(const BlockScore<NT, SPLIT, MK>& b, const Poses& poses, int np,
+                                            ScoreSlots out) {
+  block_score_tasks(b, poses, np, out);
+  __syncthreads();
+  block_score_drain(b, poses, out);
+  __syncthreads();
+}
+
+// The particle filters' choice over a wave: the first minimum of err_of(j, n)
+// over j in [0, np) by (error, index) (track::before; n: a payload that
+// travels with the error). Every lane ends with the same (be, bj, bn); bj =
+// 0x7fffffff when np == 0. Seeded with (DBL_MAX, 0x7fffffff), before() takes
+// a lane's first element whatever its error, as j < 0x7fffffff -- the choice
+// the pipeline kernels' `e < be || bj == 0x7fffffff` made -- and a lane's
+// indices ascend, so a later equal error never displaces an earlier one.
+template <class ErrOf>
+__device__ __forceinline__ void wave_argmin(int np, const ErrOf& err_of, double& be, int& bj, int32_t& bn) {
+  be = DBL_MAX;
+  bj = 0x7fffffff;
+  bn = 0;
+  for (int j = (int)(threadIdx.x & 63); j < np; j += 64) {
+    int32_t n = 0;
+    const double e = err_of(j, n);
+    if (track::before(e, j, be, bj)) { be = e; bj = j; bn = n; }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const double oe = __shfl_xor(be, o);
+    const int oj = __shfl_xor(bj, o);
+    const int32_t on = __shfl_xor(bn, o);
+    if (track::before(oe, oj, be, bj)) { be = oe; bj = oj; bn = on; }
   }
 }
 
@@ -4738,7 +4837,7 @@ __device__ inline void block_drain(UQueue q, const double* lmd, const Cam* cmp, 
 // publishing code (VGPRs bound the waves a CU keeps in flight):
 //   k_score_init   evaluateHypotheses(C hyps) + getBestNHypotheses(1)
 //   k_score_pf     optimizeHypothesisWithParticleFilter (10 x 50)
-//   k_score_final  81 shifts, top-20, determineBestYaw, publish gate
+//   k_score_final  the 81 shifts' errors, top-20, determineBestYaw, publish gate
 // init / final: 10 waves per frame. Particle filter block: 16 waves, tasks = (particle, 1/kPfSplit of the
 // landmarks): 100 tasks over 16 waves at split 2 -- 18.3 ms per 4096 frames
 // against 20.5 for 10 waves with one task per particle (50 tasks, 5 rounds)
@@ -4753,9 +4852,8 @@ constexpr int kPfSplit = MK_PF_SPLIT;
 #ifndef MK_SCORE_TAIL_THREADS
 #define MK_SCORE_TAIL_THREADS 1024
 #endif
-// k_score_final block size (>= 128: 81 shift lanes): 16 waves take the 81
-// shifted hypotheses in 6 rounds instead of 9 (128 VGPRs with some spills;
-// score stage 18.4 -> 17.5 ms per 4096 frames)
+// k_score_final / k_score_shift_part block size (>= 128: 81 shift lanes, and
+// the 80 COLOR scorings of the yaw sets over 16 waves)
 constexpr int kScoreTail = MK_SCORE_TAIL_THREADS;
 #ifndef MK_SCORE_INIT_THREADS
 #define MK_SCORE_INIT_THREADS 1024
@@ -4811,49 +4909,36 @@ __device__ inline void score_early_result(const FrameState& s, mantis_cam_result
 }
 
 // evaluateHypotheses(C hyps) + getBestNHypotheses(1) of one frame, by the
-// whole block (k_score_init, or k_score_pf taking the init itself): screened
-// tasks (hypothesis, landmark half; a wave's half in wl), the unsure
-// landmarks exactly, errors and debug records, the best one by a unique-
-// minimum reduction or, on ties, the libstdc++-order sort. ei / hs / hn hold
+// whole block (k_score_init, or k_score_pf taking the init itself): the block
+// scorer over (hypothesis, landmark half) tasks, errors and debug records,
+// the best one by a unique-minimum reduction or, on ties, the libstdc++-order
+// sort (its stack: kSortLdsBytes of static LDS, mk_sort.h). ei / hs / hn hold
 // C entries (LDS, or global scratch for more hypotheses than the LDS takes);
 // the first npfi hypotheses' screen poses are staged in pfi. Leaves the best
 // in cur (and sst), the scored count in nsc. Ends on a barrier.
+struct InitPoses {
+  const HypRec* Hh;
+  const PoseF* pfi;
+  int npfi;
+  __device__ PoseF pf(int h) const { return h < npfi ? pfi[h] : posef_from(Hh[h].c2w); }
+  __device__ const Xf& c2w(int h) const { return Hh[h].c2w; }
+};
 template <int NT, class MK>
-__device__ inline void block_score_init(const FrameDesc& fd, const Cam* cmp, const MK& mask, const Landmarks& lmk,
-                                        const WaveLms<kScrUnroll>& wl, HypRec* Hh, int C, FrameDebug& D, ErrIdx* ei,
-                                        unsigned long long* hs, int32_t* hn, PoseF* pfi, int npfi, UQueue q,
-                                        int32_t* uqn, PoseLds& cur, int32_t& nsc, int32_t& uniq_bi, ScoreState& S) {
+__device__ inline void block_score_init(const BlockScore<NT, 2, MK>& b, HypRec* Hh, int C, FrameDebug& D, ErrIdx* ei,
+                                        unsigned long long* hs, int32_t* hn, PoseF* pfi, int npfi, PoseLds& cur,
+                                        int32_t& nsc, int32_t& uniq_bi, ScoreState& S) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int W = fd.w, H = fd.h;
-  if (tid == 0) *uqn = 0;
+  if (tid == 0) *b.q.n = 0;
   for (int h = tid; h < C; h += NT) {
     hs[h] = 0;
     hn[h] = 0;
     if (h < npfi) pfi[h] = posef_from(Hh[h].c2w);
   }
   __syncthreads();
-  // tasks = (hypothesis, half of the landmarks); the halves' sums add exactly
-  for (int t = __builtin_amdgcn_readfirstlane(wave); t < 2 * C; t += (NT / 64)) {
-    const int h = t >> 1;
-    long long s;
-    int n;
-    const PoseF P = h < npfi ? pfi[h] : posef_from(Hh[h].c2w);
-    wl.sums(P, fd.scam, W, H, fd.bgr, mask, q, h, &Hh[h].c2w, lmk.xyz, cmp, s, n);
-    if (lane == 0) {
-      atomicAdd(&hs[h], (unsigned long long)s);
-      atomicAdd(&hn[h], n);
-    }
-  }
-  __syncthreads();
-  block_drain(q, lmk.xyz, cmp, W, H, fd.bgr, mask, [&](int t) -> const Xf& { return Hh[t].c2w; },
-              [&](int t, int e) {
-                atomicAdd(&hs[t], (unsigned long long)e);
-                atomicAdd(&hn[t], 1);
-              });
-  __syncthreads();
+  block_score(b, InitPoses{Hh, pfi, npfi}, C, ScoreSlots{hs, hn});
   for (int h = tid; h < C; h += NT) {
     const int n = hn[h];
-    const double e = n <= 0 ? DBL_MAX : (double)(long long)hs[h] / ((double)n * 1.1);
+    const double e = track::error_of((long long)hs[h], n);
     Hh[h].error = e;
     Hh[h].nproj = n;
     ei[h].e = e;
@@ -4913,7 +4998,7 @@ __global__ __launch_bounds__(NT) void k_score_init(
     FrameState* st, HypRec* __restrict__ hyps, mantis_cam_result* __restrict__ res, FrameDebug* dbg,
     ScoreState* __restrict__ sst) {
   const int f = blockIdx.x;
-  const int tid = threadIdx.x, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const FrameDesc fd = frames[f];
   const MaskBits mask{mbits + (size_t)f * bstride, bits::tiled_rows(fd.h), fd.w};
   FrameDebug& D = dbg[f];
@@ -4936,11 +5021,10 @@ __global__ __launch_bounds__(NT) void k_score_init(
   }
   for (int i = tid; i < nl; i += blockDim.x) lmf[i] = lmk.xyzf[i];
   __syncthreads();
-  static_assert((NT / 64) % 2 == 0 && 64 * kScrUnroll * 2 >= 768, "one register trip per half");
-  WaveLms<kScrUnroll> wl;
-  wl.load(lmf, nl * (wave & 1) / 2, nl * ((wave & 1) + 1) / 2);
-  block_score_init<NT>(fd, &frames[f].cam, mask, lmk, wl, hyps + (size_t)f * kMaxHyps, st[f].n_hyps, D, ei, hs, hn,
-                       pfi, kInitPoses, UQueue{uqe, &uqn, kInitQueue}, &uqn, cur, nsc, uniq_bi, sst[f]);
+  BlockScore<NT, 2, MaskBits> b{fd, &frames[f].cam, lmk.xyz, mask, UQueue{uqe, &uqn, kInitQueue}};
+  b.load(lmf, nl);
+  block_score_init<NT>(b, hyps + (size_t)f * kMaxHyps, st[f].n_hyps, D, ei, hs, hn, pfi, kInitPoses, cur, nsc, uniq_bi,
+                       sst[f]);
 }
 
 // computeAllShiftedHypothesesFAST (HypothesisEvaluation.h): the 9 x 9 grid of
@@ -4961,13 +5045,9 @@ __device__ inline void shift_pose(const Xf& w2c, const double* shv, int j, PoseL
 }
 
 // particle pose of the six gaussians g6 around the current pose
+// (track::particle with the reference's sigmas: |angle| < 2 rad, float gaussian x 0.03)
 __device__ inline void pf_particle(const Xf& cur_w2c, const float* g6, Xf& w2c, Xf& c2w) {
-  double yaw = (double)g6[0] * 0.03, pitch = (double)g6[1] * 0.03, roll = (double)g6[2] * 0.03;
-  double tz = (double)g6[3] * 0.01, ty = (double)g6[4] * 0.01, tx = (double)g6[5] * 0.01;
-  Xf rnd;
-  basis_from_rpy_small(roll, pitch, yaw, rnd.R);  // |angle| < 2 rad: float gaussian x 0.03
-  rnd.t[0] = tx; rnd.t[1] = ty; rnd.t[2] = tz;
-  w2c = xf_mul(cur_w2c, rnd);
+  w2c = track::particle(cur_w2c, g6, 0.03, 0.01);
   c2w = xf_inverse(w2c);
 }
 
@@ -4975,12 +5055,43 @@ __device__ inline void pf_particle(const Xf& cur_w2c, const float* g6, Xf& w2c, 
 // w2c_sample * rand, rand = Transform(setRPY(g,g,g), (g,g,g)) drawn yaw, pitch,
 // roll, z, y, x; best = first strict minimum (argmin by (error, index) over
 // the 50, taken only when strictly below the current error).
+//
+// The kernel's static LDS is PfLds and the serial sort's stack (mk_sort.h);
+// the frame's tiled mask is dynamic LDS beside it when both fit a CU's 160 KB
+// (mantis_create asks the runtime). PfLds is that budget: the assert below
+// keeps a 1280 x 720 frame on the LDS path.
+template <int SPLIT>
+struct PfLds {
+  // bytes of the particle arrays, which the init phase uses first for its per-
+  // hypothesis errors, sums and counts: C * kPer <= kBuf decides which frames
+  // run the init out of LDS (the particles' own arrays need less)
+  static constexpr int kBuf = 96 * (2 * (int)sizeof(Xf) + (int)sizeof(PoseF) + 8 + SPLIT * 12);
+  float4 lmf[768];
+  union alignas(16) {
+    struct {
+      Xf Pc[96], Pw[96];  // particles (then the 81 shifts): c2w, w2c
+      PoseF Pf[96];       // c2w as the screen reads it
+      unsigned long long Ps[96];  // one slot per particle
+      int32_t Pn[96];
+    } p;
+    unsigned char init[kBuf];
+  };
+  uint32_t uqe[kPfQueue];
+  int32_t uqn;
+  Xf cur_c2w, cur_w2c;
+  double cur_err;
+  PoseLds icur;  // the init phase's best hypothesis
+  int32_t insc, iuniq;
+  double shv[9];  // the shift phase's grid values
+};
+static_assert(sizeof(PfLds<kPfSplit>) + kSortLdsBytes + bits::tiled_words(1280, 720) * 4 <= 160 * 1024,
+              "k_score_pf's static LDS leaves no room for a 720p mask: 720p would fall back to the global-mask kernel");
 template <int NT, int SPLIT, bool LM>
 __global__ __launch_bounds__(NT) void k_score_pf(
     const FrameDesc* __restrict__ frames, const uint32_t* __restrict__ mbits, size_t bstride, Landmarks lmk,
     const FrameState* __restrict__ st, const float* __restrict__ gauss, mantis_cam_result* __restrict__ res,
-    FrameDebug* dbg, ScoreState* __restrict__ sst, int particles, int iterations, int shifts, double grid_spacing,
-    int grid_size, int init, HypRec* __restrict__ hyps, unsigned char* __restrict__ init_scratch) {
+    FrameDebug* dbg, ScoreState* __restrict__ sst, int particles, int iterations, double grid_spacing, int grid_size,
+    int init, HypRec* __restrict__ hyps, unsigned char* __restrict__ init_scratch) {
   const int f = blockIdx.x;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   if (!st[f].reaches_pf) {
@@ -5000,23 +5111,15 @@ __global__ __launch_bounds__(NT) void k_score_pf(
   }
   FrameDebug& D = dbg[f];
   const int nl = lmk.nw + lmk.nr + lmk.ng;
-  __shared__ float4 lmf[768];
-  // the particles' poses and sums (Pc, Pw, Pf, Pe, Ps, Pn) in one buffer, which
-  // the init phase (init: k_score_init's work done here, the mask already in
-  // LDS) uses first for its per-hypothesis errors, sums and counts
-  constexpr int kPfBuf = 96 * (2 * (int)sizeof(Xf) + (int)sizeof(PoseF) + 8 + SPLIT * 12);
-  __shared__ __align__(16) unsigned char pbuf[kPfBuf];
-  Xf* Pc = (Xf*)pbuf;
-  Xf* Pw = Pc + 96;
-  PoseF* Pf = (PoseF*)(Pw + 96);
-  double* Pe = (double*)(Pf + 96);
-  unsigned long long* Ps = (unsigned long long*)(Pe + 96);
-  int32_t* Pn = (int32_t*)(Ps + 96 * SPLIT);
-  __shared__ uint32_t uqe[kPfQueue];
-  __shared__ int32_t uqn;
-  constexpr int kW = NT / 64;
-  __shared__ Xf cur_c2w, cur_w2c;
-  __shared__ double cur_err;
+  __shared__ PfLds<SPLIT> L;
+  constexpr int kPfBuf = PfLds<SPLIT>::kBuf;
+  float4* lmf = L.lmf;
+  Xf *Pc = L.p.Pc, *Pw = L.p.Pw;
+  PoseF* Pf = L.p.Pf;
+  const ScoreSlots slots{L.p.Ps, L.p.Pn};
+  int32_t& uqn = L.uqn;
+  Xf &cur_c2w = L.cur_c2w, &cur_w2c = L.cur_w2c;
+  double& cur_err = L.cur_err;
   for (int i = tid; i < nl; i += blockDim.x) lmf[i] = lmk.xyzf[i];
   if (tid == 0 && !init) {
     cur_c2w = sst[f].cur.c2w;
@@ -5039,24 +5142,22 @@ __global__ __launch_bounds__(NT) void k_score_pf(
 #endif
   MK_PTICK(0);
   const float* gs = gauss + st[f].gauss_offset;
-  const UQueue q{uqe, &uqn, kPfQueue};
-  const MaskLds mlds{(lds_cu32*)pf_mask, bits::tiled_rows(H)};
-  const MaskBits mglb{fm, bits::tiled_rows(H), W};
+  using PfMask = typename std::conditional<LM, MaskLds, MaskBits>::type;
   // a wave's tasks are (particle, slice wave % SPLIT): its slice of the
   // landmarks stays in registers for every task and iteration
-  static_assert(kW % SPLIT == 0 && 64 * kScrUnroll * SPLIT >= 768, "one register trip per slice");
-  WaveLms<kScrUnroll> wl;
-  {
-    const int h = wave % SPLIT;
-    wl.load(lmf, nl * h / SPLIT, nl * (h + 1) / SPLIT);
-  }
+  const auto mask = [&] {  // the LDS / global choice, made once
+    if constexpr (LM) return MaskLds{(lds_cu32*)pf_mask, bits::tiled_rows(H)};
+    else return MaskBits{fm, bits::tiled_rows(H), W};
+  }();
+  BlockScore<NT, SPLIT, PfMask> b{fd, &frames[f].cam, lmk.xyz, mask, UQueue{L.uqe, &L.uqn, kPfQueue}};
+  b.load(lmf, nl);
+  const StagedPoses poses{Pf, Pc};
   if (init) {
     // evaluateHypotheses + getBestNHypotheses(1) (k_score_init's block
     // function) with the mask lookups from LDS; the init's landmark halves are
     // the particle tasks' slices (SPLIT == 2)
     static_assert(SPLIT == 2, "the init tasks use landmark halves");
-    __shared__ PoseLds icur;
-    __shared__ int32_t insc, iuniq;
+    PoseLds& icur = L.icur;
     const int C = st[f].n_hyps;
     HypRec* Hh = hyps + (size_t)f * kMaxHyps;
     constexpr int kPer = (int)(sizeof(ErrIdx) + sizeof(unsigned long long) + sizeof(int32_t));
@@ -5064,13 +5165,9 @@ __global__ __launch_bounds__(NT) void k_score_pf(
       ErrIdx* ei = (ErrIdx*)buf;
       unsigned long long* hs = (unsigned long long*)(ei + C);
       int32_t* hn = (int32_t*)(hs + C);
-      const UQueue qi{uqe, &uqn, kPfQueue};
-      if (LM) block_score_init<NT>(fd, &frames[f].cam, mlds, lmk, wl, Hh, C, D, ei, hs, hn, nullptr, 0, qi, &uqn,
-                                   icur, insc, iuniq, sst[f]);
-      else block_score_init<NT>(fd, &frames[f].cam, mglb, lmk, wl, Hh, C, D, ei, hs, hn, nullptr, 0, qi, &uqn, icur,
-                                insc, iuniq, sst[f]);
+      block_score_init<NT>(b, Hh, C, D, ei, hs, hn, nullptr, 0, icur, L.insc, L.iuniq, sst[f]);
     };
-    if (C * kPer <= kPfBuf && init != 2) run(pbuf);  // init == 2 (tests): the global-scratch path
+    if (C * kPer <= kPfBuf && init != 2) run(L.init);  // init == 2 (tests): the global-scratch path
     else run(init_scratch + (size_t)f * kMaxHyps * kPer);  // more hypotheses than the LDS buffer takes: global scratch
     if (tid == 0) {
       cur_c2w = icur.c2w;
@@ -5083,7 +5180,7 @@ __global__ __launch_bounds__(NT) void k_score_pf(
   // once every wave holds its slice (wl) -- the particle phase then reads them
   // by ds_read instead of a global round trip per iteration
   const int ngs = particles * iterations * 6;
-  const bool gl = ngs <= (int)(sizeof(lmf) / sizeof(float));
+  const bool gl = ngs <= (int)(sizeof(L.lmf) / sizeof(float));
   float* glds = (float*)lmf;
   __syncthreads();
   if (gl)
@@ -5099,6 +5196,12 @@ __global__ __launch_bounds__(NT) void k_score_pf(
   __syncthreads();
   if (iterations > 0)
     for (int j = tid; j < particles; j += NT) particle(0, j, cur_w2c);
+  // the scorer's precondition: slots and queue count zero behind a barrier --
+  // here for the first iteration, by wave 0 at the end of an iteration for the next
+  for (int j = tid; j < particles; j += NT) {
+    slots.s[j] = 0;
+    slots.n[j] = 0;
+  }
   if (tid == 0) uqn = 0;
   __syncthreads();
   MK_PTICK(1);
@@ -5108,46 +5211,18 @@ __global__ __launch_bounds__(NT) void k_score_pf(
   for (int it = 0; it < iterations; it++) {
     // SPLIT waves per particle (landmark slices; integer sums, so the
     // partials combine exactly in any order); a wave's tasks pipelined
-    for (int task = __builtin_amdgcn_readfirstlane(wave); task < particles * SPLIT; task += kW) {
-      const int j = task / SPLIT;
-      long long sum;
-      int cnt;
-      if (LM) wl.sums(Pf[j], fd.scam, W, H, fd.bgr, mlds, q, j, &Pc[j], lmk.xyz, &frames[f].cam, sum, cnt);
-      else wl.sums(Pf[j], fd.scam, W, H, fd.bgr, mglb, q, j, &Pc[j], lmk.xyz, &frames[f].cam, sum, cnt);
-      if (lane == 0) {
-        Ps[task] = (unsigned long long)sum;
-        Pn[task] = cnt;
-      }
-    }
+    block_score_tasks(b, poses, particles, slots);
     __syncthreads();
     MK_PTICK(2);
-    const auto pose_of = [&](int t) -> const Xf& { return Pc[t]; };
-    const auto add = [&](int t, int e) {
-      atomicAdd(&Ps[t * SPLIT], (unsigned long long)e);
-      atomicAdd(&Pn[t * SPLIT], 1);
-    };
-    if (LM) block_drain(q, lmk.xyz, &frames[f].cam, W, H, fd.bgr, mlds, pose_of, add);
-    else block_drain(q, lmk.xyz, &frames[f].cam, W, H, fd.bgr, mglb, pose_of, add);
+    block_score_drain(b, poses, slots);
     __syncthreads();
     MK_PTICK(3);
     if (wave == 0) {
-      double be = DBL_MAX;
-      int bj = 0x7fffffff;
-      for (int j = lane; j < particles; j += 64) {
-        long long sum = 0;
-        int cnt = 0;
-        for (int h = 0; h < SPLIT; h++) {
-          sum += (long long)Ps[j * SPLIT + h];
-          cnt += Pn[j * SPLIT + h];
-        }
-        const double e = cnt <= 0 ? DBL_MAX : (double)sum / ((double)cnt * 1.1);
-        if (e < be || bj == 0x7fffffff) { be = e; bj = j; }
-      }
-      for (int o = 32; o > 0; o >>= 1) {
-        const double oe = __shfl_xor(be, o);
-        const int oj = __shfl_xor(bj, o);
-        if (oe < be || (oe == be && oj < bj)) { be = oe; bj = oj; }
-      }
+      double be;
+      int bj;
+      int32_t bn;
+      wave_argmin(particles, [&](int j, int32_t&) { return track::error_of((long long)slots.s[j], slots.n[j]); }, be,
+                  bj, bn);
       MK_PTICK(4);
       // the winner (wave-uniform) read by every lane before any lane
       // overwrites the particle arrays with the next iteration's
@@ -5161,6 +5236,10 @@ __global__ __launch_bounds__(NT) void k_score_pf(
         }
         if (it + 1 < (int)(sizeof(D.pf_iter_err) / sizeof(double))) D.pf_iter_err[it + 1] = upd ? be : cur_err;  // the record holds 10 iterations
         uqn = 0;
+      }
+      for (int j = lane; j < particles; j += 64) {  // the slots this lane read in the argmin
+        slots.s[j] = 0;
+        slots.n[j] = 0;
       }
       if (it + 1 < iterations)
         for (int j = lane; j < particles; j += 64) particle(it + 1, j, nw);
@@ -5185,15 +5264,14 @@ __global__ __launch_bounds__(NT) void k_score_pf(
     D.pf_err = cur_err;
     res[f].pf_error = cur_err;
   }
-  if (!shifts) return;
   // shifts (round 6): the 81 shifted hypotheses of k_score_final scored here,
   // while the frame's mask is still in LDS (lookups by ds_read instead of L2
   // gathers); their integer sums and counts go to ScoreState, where
-  // k_score_final (pre) takes them, as after k_score_shift_part. Same poses
+  // k_score_final takes them, as after k_score_shift_part. Same poses
   // (shift_pose of the same optimum), same sums.
   constexpr int NS = 81;
   static_assert(NS <= 96, "shift poses in the particle arrays");
-  __shared__ double shv[9];
+  double* shv = L.shv;
   if (tid == 0) {
     uqn = 0;
     shift_values(grid_size, grid_spacing, shv);
@@ -5204,43 +5282,14 @@ __global__ __launch_bounds__(NT) void k_score_pf(
     shift_pose(cur_w2c, shv, tid, o);
     Pc[tid] = o.c2w;
     Pf[tid] = posef_from(o.c2w);
-  }
-  for (int i = tid; i < NS * SPLIT; i += NT) {
-    Ps[i] = 0;
-    Pn[i] = 0;
+    slots.s[tid] = 0;
+    slots.n[tid] = 0;
   }
   __syncthreads();
-  for (int task = __builtin_amdgcn_readfirstlane(wave); task < NS * SPLIT; task += kW) {
-    const int j = task / SPLIT;
-    long long sum;
-    int cnt;
-    if (LM) wl.sums(Pf[j], fd.scam, W, H, fd.bgr, mlds, q, j, &Pc[j], lmk.xyz, &frames[f].cam, sum, cnt);
-    else wl.sums(Pf[j], fd.scam, W, H, fd.bgr, mglb, q, j, &Pc[j], lmk.xyz, &frames[f].cam, sum, cnt);
-    if (lane == 0) {
-      Ps[task] = (unsigned long long)sum;
-      Pn[task] = cnt;
-    }
-  }
-  __syncthreads();
-  {
-    const auto pose_of = [&](int t) -> const Xf& { return Pc[t]; };
-    const auto add = [&](int t, int e) {
-      atomicAdd(&Ps[t * SPLIT], (unsigned long long)e);
-      atomicAdd(&Pn[t * SPLIT], 1);
-    };
-    if (LM) block_drain(q, lmk.xyz, &frames[f].cam, W, H, fd.bgr, mlds, pose_of, add);
-    else block_drain(q, lmk.xyz, &frames[f].cam, W, H, fd.bgr, mglb, pose_of, add);
-  }
-  __syncthreads();
+  block_score(b, poses, NS, slots);
   if (tid < NS) {
-    long long sum = 0;
-    int cnt = 0;
-    for (int h = 0; h < SPLIT; h++) {
-      sum += (long long)Ps[tid * SPLIT + h];
-      cnt += Pn[tid * SPLIT + h];
-    }
-    sst[f].psum[tid] = sum;
-    sst[f].pcnt[tid] = cnt;
+    sst[f].psum[tid] = (long long)slots.s[tid];
+    sst[f].pcnt[tid] = slots.n[tid];
   }
 }
 
@@ -5286,31 +5335,10 @@ __global__ __launch_bounds__(NT) void k_score_pf_part(
   }
   if (tid == 0) uqn = 0;
   __syncthreads();
-  const UQueue q{uqe, &uqn, kPfQueue};
-  const MaskBits mglb{mbits + (size_t)f * bstride, bits::tiled_rows(H), W};
-  static_assert(kW % SPLIT == 0 && 64 * kScrUnroll * SPLIT >= 768, "one register trip per slice");
-  WaveLms<kScrUnroll> wl;
-  {
-    const int h = wave % SPLIT;
-    wl.load(lmf, nl * h / SPLIT, nl * (h + 1) / SPLIT);
-  }
-  for (int task = __builtin_amdgcn_readfirstlane(wave); task < np * SPLIT; task += kW) {
-    const int j = task / SPLIT;
-    long long sum;
-    int cnt;
-    wl.sums(Pf[j], fd.scam, W, H, fd.bgr, mglb, q, j, &Pc[j], lmk.xyz, &frames[f].cam, sum, cnt);
-    if (lane == 0) {
-      atomicAdd(&Ps[j], (unsigned long long)sum);
-      atomicAdd(&Pn[j], cnt);
-    }
-  }
-  __syncthreads();
-  block_drain(q, lmk.xyz, &frames[f].cam, W, H, fd.bgr, mglb, [&](int t) -> const Xf& { return Pc[t]; },
-              [&](int t, int e) {
-                atomicAdd(&Ps[t], (unsigned long long)e);
-                atomicAdd(&Pn[t], 1);
-              });
-  __syncthreads();
+  const MaskBits mask{mbits + (size_t)f * bstride, bits::tiled_rows(H), W};
+  BlockScore<NT, SPLIT, MaskBits> bs{fd, &frames[f].cam, lmk.xyz, mask, UQueue{uqe, &uqn, kPfQueue}};
+  bs.load(lmf, nl);
+  block_score(bs, StagedPoses{Pf, Pc}, np, ScoreSlots{Ps, Pn});
   if (tid < np) {
     S.psum[p0 + tid] = (long long)Ps[tid];
     S.pcnt[p0 + tid] = Pn[tid];
@@ -5325,18 +5353,13 @@ __global__ __launch_bounds__(NT) void k_score_pf_part(
   __threadfence();
   const volatile long long* vs = S.psum;
   const volatile int32_t* vc = S.pcnt;
-  double be = DBL_MAX;
-  int bj = 0x7fffffff;
-  for (int j = lane; j < particles; j += 64) {
+  double be;
+  int bj;
+  int32_t bn;
+  wave_argmin(particles, [&](int j, int32_t&) {
     const int cnt = vc[j];
-    const double e = cnt <= 0 ? DBL_MAX : (double)vs[j] / ((double)cnt * 1.1);
-    if (e < be || bj == 0x7fffffff) { be = e; bj = j; }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const double oe = __shfl_xor(be, o);
-    const int oj = __shfl_xor(bj, o);
-    if (oe < be || (oe == be && oj < bj)) { be = oe; bj = oj; }
-  }
+    return track::error_of(vs[j], cnt);
+  }, be, bj, bn);
   if (lane == 0) {
     FrameDebug& D = dbg[f];
     if (bj < particles && be < S.cur.err) {
@@ -5359,13 +5382,65 @@ __global__ __launch_bounds__(NT) void k_score_pf_part(
   }
 }
 
+// Rig tracking's and MCL's scoring block (k_track_score, track_impl.hip;
+// k_mcl_score, mcl_impl.hip): poses prepared by another kernel, in FP64 (c2w)
+// and as the screen reads them (pf), task (particle j, camera) at index
+// t0 + j * C + cam of c2w / pf / sums / cnt. The block takes particles
+// [chunk * kPP, ...) of np on frame f, each a task per landmark slice (one per
+// wave), and stores (sum, n) of each of its (particle, camera) -- owned by
+// this block alone -- with one plain store.
+template <int NT, int SPLIT>
+__device__ __forceinline__ void pose_score_block(const FrameDesc* __restrict__ frames,
+                                                 const uint32_t* __restrict__ mbits, size_t bstride,
+                                                 const Landmarks& lmk, const Xf* __restrict__ c2w,
+                                                 const PoseF* __restrict__ pf, long long* __restrict__ sums,
+                                                 int32_t* __restrict__ cnt, size_t t0, int C, int f, int cam,
+                                                 int chunk, int np) {
+  const int tid = threadIdx.x;
+  constexpr int kPP = NT / 64 / SPLIT;  // particles per block (one task per wave)
+  static_assert(kPP >= 1, "a wave per slice");
+  const FrameDesc fd = frames[f];
+  const int nl = lmk.nw + lmk.nr + lmk.ng;
+  __shared__ float4 lmf[768];
+  __shared__ Xf Pc[kPP];
+  __shared__ PoseF Pf[kPP];
+  __shared__ unsigned long long Ps[kPP];
+  __shared__ int32_t Pn[kPP];
+  __shared__ uint32_t uqe[kPfQueue];
+  __shared__ int32_t uqn;
+  const int j0 = chunk * kPP, nj = max(0, min(kPP, np - j0));
+  for (int i = tid; i < nl; i += NT) lmf[i] = lmk.xyzf[i];
+  if (tid < nj) {
+    const size_t t = t0 + (size_t)(j0 + tid) * C + cam;
+    Pc[tid] = c2w[t];
+    Pf[tid] = pf[t];
+    Ps[tid] = 0;
+    Pn[tid] = 0;
+  }
+  if (tid == 0) uqn = 0;
+  __syncthreads();
+  const MaskBits mask{mbits + (size_t)f * bstride, bits::tiled_rows(fd.h), fd.w};
+  BlockScore<NT, SPLIT, MaskBits> b{fd, &frames[f].cam, lmk.xyz, mask, UQueue{uqe, &uqn, kPfQueue}};
+  b.load(lmf, nl);
+  block_score(b, StagedPoses{Pf, Pc}, nj, ScoreSlots{Ps, Pn});
+  if (tid < nj) {
+    const size_t t = t0 + (size_t)(j0 + tid) * C + cam;
+    sums[t] = (long long)Ps[tid];
+    cnt[t] = Pn[tid];
+  }
+}
+
 // computeAllShiftedHypothesesFAST's shift values (accumulated in double as the
 // reference loop does) and shifted pose j = (j / 9, j % 9) of the optimum
 // The 81 shifted hypotheses' screened sums spread over `nblk` blocks per frame
 // (small batches): block b takes shifts [b * spb, (b+1) * spb), one task per
 // (shift, landmark half), drains its own unsure landmarks, and writes each
-// shift's integer sum and count to ScoreState; k_score_final (pre = true)
-// takes them from there instead of scoring the shifts itself. Same sums.
+// shift's integer sum and count to ScoreState, where k_score_final takes them.
+struct ShiftPoses {  // the screen pose converted per task
+  const PoseLds* P;
+  __device__ PoseF pf(int j) const { return posef_from(P[j].c2w); }
+  __device__ const Xf& c2w(int j) const { return P[j].c2w; }
+};
 template <int NT>
 __global__ __launch_bounds__(NT) void k_score_shift_part(
     const FrameDesc* __restrict__ frames, const uint32_t* __restrict__ mbits, size_t bstride, Landmarks lmk,
@@ -5398,27 +5473,9 @@ __global__ __launch_bounds__(NT) void k_score_shift_part(
     hn[tid] = 0;
   }
   __syncthreads();
-  const UQueue q{uqe, &uqn, kTailQueue};
-  static_assert((NT / 64) % 2 == 0 && 64 * kScrUnroll * 2 >= 768, "one register trip per half");
-  WaveLms<kScrUnroll> wl;
-  wl.load(lmf, nl * (wave & 1) / 2, nl * ((wave & 1) + 1) / 2);
-  for (int t = __builtin_amdgcn_readfirstlane(wave); t < 2 * ns; t += NT / 64) {
-    const int j = t >> 1;
-    long long sum;
-    int n;
-    wl.sums(posef_from(P[j].c2w), fd.scam, W, H, fd.bgr, mask, q, j, &P[j].c2w, lmk.xyz, &frames[f].cam, sum, n);
-    if (lane == 0) {
-      atomicAdd(&hs[j], (unsigned long long)sum);
-      atomicAdd(&hn[j], n);
-    }
-  }
-  __syncthreads();
-  block_drain(q, lmk.xyz, &frames[f].cam, W, H, fd.bgr, mask, [&](int t) -> const Xf& { return P[t].c2w; },
-              [&](int t, int e) {
-                atomicAdd(&hs[t], (unsigned long long)e);
-                atomicAdd(&hn[t], 1);
-              });
-  __syncthreads();
+  BlockScore<NT, 2, MaskBits> bs{fd, &frames[f].cam, lmk.xyz, mask, UQueue{uqe, &uqn, kTailQueue}};
+  bs.load(lmf, nl);
+  block_score(bs, ShiftPoses{P}, ns, ScoreSlots{hs, hn});
   if (tid < ns) {
     sst[f].psum[j0 + tid] = (long long)hs[tid];
     sst[f].pcnt[j0 + tid] = hn[tid];
@@ -5427,19 +5484,16 @@ __global__ __launch_bounds__(NT) void k_score_shift_part(
 
 template <int NT>
 __global__ __launch_bounds__(NT) void k_score_final(
-    const FrameDesc* __restrict__ frames, const uint32_t* __restrict__ mbits, size_t bstride, Landmarks lmk,
-    const FrameState* __restrict__ st, mantis_cam_result* __restrict__ res, FrameDebug* dbg,
-    const ScoreState* __restrict__ sst, double grid_spacing, int grid_size, bool pre) {
+    const FrameDesc* __restrict__ frames, Landmarks lmk, const FrameState* __restrict__ st,
+    mantis_cam_result* __restrict__ res, FrameDebug* dbg, const ScoreState* __restrict__ sst, double grid_spacing,
+    int grid_size) {
   const int f = blockIdx.x;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   if (!st[f].reaches_pf) return;
   const FrameDesc fd = frames[f];
   const int W = fd.w, H = fd.h;
-  const MaskBits mask{mbits + (size_t)f * bstride, bits::tiled_rows(H), W};
   mantis_cam_result& R = res[f];
   FrameDebug& D = dbg[f];
-  const int nl = lmk.nw + lmk.nr + lmk.ng;
-  __shared__ float4 lmf[768];
   __shared__ PoseLds P[96];
   __shared__ ErrIdx ei[96];
   // COLOR phase: the block path's pair table, or (maps with more than
@@ -5450,10 +5504,6 @@ __global__ __launch_bounds__(NT) void k_score_final(
   __shared__ double shv[9];
   __shared__ double yerr[4];
   __shared__ int32_t nsc;
-  __shared__ unsigned long long hs[96];
-  __shared__ int32_t hn[96];
-  __shared__ uint32_t uqe[kTailQueue];
-  __shared__ int32_t uqn;
 #if defined(MK_SCORE_TICKS) && MK_SCORE_TICKS != 2  // diagnostics: phase ends of this kernel into st[f].ticks (10 ns), tools/score_ticks.py
   const uint64_t tk0 = wall_clock64();
   int32_t* tk = const_cast<FrameState*>(st)[f].ticks;
@@ -5462,53 +5512,19 @@ __global__ __launch_bounds__(NT) void k_score_final(
 #else
 #define MK_STICK(k)
 #endif
-  for (int i = tid; i < nl; i += blockDim.x) lmf[i] = lmk.xyzf[i];
   if (tid == 0) {
-    uqn = 0;
     cur = sst[f].cur;
     nsc = sst[f].nsc;
     shift_values(grid_size, grid_spacing, shv);
   }
   __syncthreads();
-  // computeAllShiftedHypothesesFAST: 81 shifted copies of the optimum
+  // computeAllShiftedHypothesesFAST: 81 shifted copies of the optimum; their
+  // integer sums were left in ScoreState by k_score_pf's shift phase (large
+  // batches) or k_score_shift_part (small ones)
   const int NS = 81;
-  if (tid < NS) shift_pose(cur.w2c, shv, tid, P[tid]);
-  __syncthreads();
-  const UQueue q{uqe, &uqn, kTailQueue};
   if (tid < NS) {
-    hs[tid] = pre ? (unsigned long long)sst[f].psum[tid] : 0ull;  // pre: k_score_shift_part's sums
-    hn[tid] = pre ? sst[f].pcnt[tid] : 0;
-  }
-  __syncthreads();
-  if (!pre) {
-  // tasks = (shift, half of the landmarks): 162 one-trip tasks over the waves
-  // instead of 81 two-trip ones (the last round of whole hypotheses kept one
-  // wave busy); the halves' integer sums combine exactly
-  static_assert((NT / 64) % 2 == 0 && 64 * kScrUnroll * 2 >= 768, "one register trip per half");
-  WaveLms<kScrUnroll> wl;
-  wl.load(lmf, nl * (wave & 1) / 2, nl * ((wave & 1) + 1) / 2);
-  for (int t = __builtin_amdgcn_readfirstlane(wave); t < 2 * NS; t += (NT / 64)) {
-    const int j = t >> 1;
-    long long sum;
-    int n;
-    wl.sums(posef_from(P[j].c2w), fd.scam, W, H, fd.bgr, mask, q, j, &P[j].c2w, lmk.xyz, &frames[f].cam, sum, n);
-    if (lane == 0) {
-      atomicAdd(&hs[j], (unsigned long long)sum);
-      atomicAdd(&hn[j], n);
-    }
-  }
-  __syncthreads();
-  MK_STICK(0);
-  block_drain(q, lmk.xyz, &frames[f].cam, W, H, fd.bgr, mask, [&](int t) -> const Xf& { return P[t].c2w; },
-              [&](int t, int e) {
-                atomicAdd(&hs[t], (unsigned long long)e);
-                atomicAdd(&hn[t], 1);
-              });
-  __syncthreads();
-  }
-  if (tid < NS) {
-    const int n = hn[tid];
-    const double e = n <= 0 ? DBL_MAX : (double)(long long)hs[tid] / ((double)n * 1.1);
+    shift_pose(cur.w2c, shv, tid, P[tid]);
+    const double e = track::error_of(sst[f].psum[tid], sst[f].pcnt[tid]);
     P[tid].err = e;
     ei[tid].e = e;
     ei[tid].i = tid;
@@ -5731,12 +5747,16 @@ __global__ __launch_bounds__(256) void k_rig_weight(const FrameDesc* __restrict_
 #define MK_DENSE_HYPS 64
 #endif
 constexpr int kApiHyps = 16, kApiQueue = 1024, kDenseHyps = MK_DENSE_HYPS;
+struct ApiPoses {  // the caller's n x 12 doubles (R[9], t[3] = mk::Xf) from the block's first; screen poses staged
+  const PoseF* f;
+  const double* c;
+  __device__ const PoseF& pf(int j) const { return f[j]; }
+  __device__ const Xf& c2w(int j) const { return *(const Xf*)(c + 12 * (size_t)j); }
+};
 template <int HPB, class MK>
 __device__ inline void score_api_fast(const FrameDesc& fd, const Cam* cmp, const MK& mask, Landmarks lmk,
                                       const double* c2w, int n, double* err, int32_t* nproj) {
-  constexpr int NW = kApiHyps;  // waves per block
-  static_assert(NW % 2 == 0 && 64 * kScrUnroll * 2 >= 768, "one register trip per half");
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int h0 = blockIdx.x * HPB, nh = min(HPB, n - h0);
   const int nl = lmk.nw + lmk.nr + lmk.ng;
   __shared__ float4 lmf[768];
@@ -5753,32 +5773,12 @@ __device__ inline void score_api_fast(const FrameDesc& fd, const Cam* cmp, const
   }
   if (tid == 0) uqn = 0;
   __syncthreads();
-  const UQueue q{uqe, &uqn, kApiQueue};
-  WaveLms<kScrUnroll> wl;
-  wl.load(lmf, nl * (wave & 1) / 2, nl * ((wave & 1) + 1) / 2);
-  for (int t = __builtin_amdgcn_readfirstlane(wave); t < 2 * nh; t += NW) {
-    const int j = t >> 1;
-    const Xf* T = (const Xf*)(c2w + 12 * (size_t)(h0 + j));  // R[9], t[3] = mk::Xf
-    long long s;
-    int c;
-    wl.sums(pf[j], fd.scam, fd.w, fd.h, fd.bgr, mask, q, j, T, lmk.xyz, cmp, s, c);
-    if (lane == 0) {
-      atomicAdd(&hs[j], (unsigned long long)s);
-      atomicAdd(&hn[j], c);
-    }
-  }
-  __syncthreads();
-  block_drain(q, lmk.xyz, cmp, fd.w, fd.h, fd.bgr, mask,
-              [&](int t) -> const Xf& { return *(const Xf*)(c2w + 12 * (size_t)(h0 + t)); },
-              [&](int t, int e) {
-                atomicAdd(&hs[t], (unsigned long long)e);
-                atomicAdd(&hn[t], 1);
-              });
-  __syncthreads();
+  BlockScore<64 * kApiHyps, 2, MK> b{fd, cmp, lmk.xyz, mask, UQueue{uqe, &uqn, kApiQueue}};
+  b.load(lmf, nl);
+  block_score(b, ApiPoses{pf, c2w + 12 * (size_t)h0}, nh, ScoreSlots{hs, hn});
   for (int i = tid; i < nh; i += blockDim.x) {
-    const int c = hn[i];
-    err[h0 + i] = c <= 0 ? DBL_MAX : (double)(long long)hs[i] / ((double)c * 1.1);
-    nproj[h0 + i] = c;
+    err[h0 + i] = track::error_of((long long)hs[i], hn[i]);
+    nproj[h0 + i] = hn[i];
   }
 }
 __global__ __launch_bounds__(64 * kApiHyps) void k_score_api(const FrameDesc* __restrict__ frames, const uint8_t* mask,

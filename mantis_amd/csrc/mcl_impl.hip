@@ -1,7 +1,6 @@
 // Monte Carlo localization: the persistent rig particle filter
 // (mantis_mcl_*, include/mantis.h). Included by api.hip (shares its Ctx, frame
-// staging and image stages) after track_impl.hip, whose scoring block it
-// reuses. The weight / scan / ancestor / estimate rules are in mk_mcl.h
+// staging and image stages). The weight / scan / ancestor / estimate rules are in mk_mcl.h
 // (shared with the host build of the tests).
 //
 // Device work of one step, all on the context stream: the image stages up to
@@ -9,8 +8,8 @@
 // the colour evidence on: k_mcl_color, mcl_color_impl.hip, after k_mcl_score):
 //   k_mcl_predict    one lane per particle: T_j <- T_j * Delta * rand_j, and per
 //                    camera the FP64 c2w and its FP32 screen pose
-//   k_mcl_score      grid (particle chunk, camera): track_score_block, the very
-//                    body of k_track_score (track_impl.hip); each (particle,
+//   k_mcl_score      grid (particle chunk, camera): pose_score_block (kernels.hip),
+//                    the body of k_track_score too; each (particle,
 //                    camera) owned by one block, (sum, n) written with one store
 //   k_mcl_weight     one block of 1024: pool, validity, L (less the colour charge
 //                    in the instantiation that folds it), Lmax, q, the integer
@@ -66,7 +65,7 @@ template <int NT, int SPLIT>
 __global__ __launch_bounds__(NT) void k_mcl_score(const FrameDesc* __restrict__ frames,
                                                   const uint32_t* __restrict__ mbits, size_t bstride, Landmarks lmk,
                                                   MclArgs a) {
-  track_score_block<NT, SPLIT>(frames, mbits, bstride, lmk, a.c2w, a.pf, a.sums, a.cnt, 0, a.C, blockIdx.y, blockIdx.y,
+  pose_score_block<NT, SPLIT>(frames, mbits, bstride, lmk, a.c2w, a.pf, a.sums, a.cnt, 0, a.C, blockIdx.y, blockIdx.y,
                                blockIdx.x, a.N);
 }
 

@@ -92,6 +92,8 @@ MK_HD ErrIdx* unguarded_partition(ErrIdx* first, ErrIdx* last, ErrIdx* pivot) {
     ++first;
   }
 }
+// static LDS a kernel that calls std_sort_desc carries for the stack below
+constexpr int kSortLdsBytes = 64 * (2 * (int)sizeof(ErrIdx*) + (int)sizeof(int));
 MK_HD void introsort_loop(ErrIdx* first, ErrIdx* last, int depth_limit) {
   // iterative form of the reference recursion: recurse on the right part,
   // loop on the left part (same visiting order, explicit stack)

@@ -24,8 +24,12 @@ constexpr int kMaxIterations = 10;  // mantis_track_params.iterations (iter_err[
 constexpr int kMaxCams = 8;         // cameras per rig
 constexpr int kMaxTasks = 512;      // particles x cameras per rig
 
-// E = (double)sum(sum_c) / ((double)sum(n_c) * 1.1), DBL_MAX when no camera
-// sees a landmark; *n_out = sum(n_c). sums / counts: one entry per camera.
+// The fast evaluator's error of an integer (sum, n): every scorer's rule
+// (HypothesisEvaluation.h:218-227), DBL_MAX when no landmark was seen.
+MK_HD double error_of(long long sum, int32_t n) { return n <= 0 ? DBL_MAX : (double)sum / ((double)n * 1.1); }
+
+// E = error_of(sum(sum_c), sum(n_c)): the cameras' sums pooled before the
+// division; *n_out = sum(n_c). sums / counts: one entry per camera.
 MK_HD double pool(const long long* sums, const int32_t* counts, int n_cams, int32_t* n_out) {
   long long s = 0;
   int32_t n = 0;
@@ -34,7 +38,7 @@ MK_HD double pool(const long long* sums, const int32_t* counts, int n_cams, int3
     n += counts[c];
   }
   *n_out = n;
-  return n <= 0 ? DBL_MAX : (double)s / ((double)n * 1.1);
+  return error_of(s, n);
 }
 
 // the argmin's order: by (error, particle index)

@@ -62,20 +62,12 @@ __global__ __launch_bounds__(64) void k_track_particles(TrackArgs a, int call) {
     // by (error, index); every lane ends with the same (be, bj, bn)
     const int pass = call - 1, np = pass == 0 ? 1 : P;
     const size_t t0 = (size_t)pass * a.pass_tasks + (size_t)rig * P * C;
-    double be = DBL_MAX;
-    int bj = 0x7fffffff;
-    int32_t bn = 0;
-    for (int j = lane; j < np; j += 64) {
-      int32_t n;
-      const double e = track::pool(a.sums + t0 + (size_t)j * C, a.cnt + t0 + (size_t)j * C, C, &n);
-      if (track::before(e, j, be, bj)) { be = e; bj = j; bn = n; }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      const double oe = __shfl_xor(be, o);
-      const int oj = __shfl_xor(bj, o);
-      const int32_t on = __shfl_xor(bn, o);
-      if (track::before(oe, oj, be, bj)) { be = oe; bj = oj; bn = on; }
-    }
+    double be;
+    int bj;
+    int32_t bn;
+    wave_argmin(np, [&](int j, int32_t& n) {
+      return track::pool(a.sums + t0 + (size_t)j * C, a.cnt + t0 + (size_t)j * C, C, &n);
+    }, be, bj, bn);
     if (pass == 0) {  // the seed's own error
       cur = S.cur;
       cur_err = be;
@@ -125,86 +117,16 @@ __global__ __launch_bounds__(64) void k_track_particles(TrackArgs a, int call) {
   }
 }
 
-// Pass `pass` of every rig on every camera: block (chunk, camera, rig) takes
-// particles [chunk * kPP, ...) of the pass (np of them: 1 for the seed), each
-// a task per landmark slice (one per wave, the slice resident in registers);
-// the slices and the block's exactly recomputed unsure landmarks add into the
-// particle's LDS sums, and the block stores (sum, n) of each of its
-// (rig, particle, camera) -- owned by this block alone -- with one plain store.
-// int32 accumulators of wave_sums_screen_t: a slice is at most 64 x
-// kScrUnroll landmarks (static_assert below), one trip, <= kScrUnroll
-// landmarks per lane.
-// The block's work as a function of where its poses and sums lie: frame f,
-// camera `cam` of C, particles [chunk * kPP, ...) of np, task (particle j,
-// camera) at index t0 + j * C + cam of c2w / pf / sums / cnt. Shared with
-// k_mcl_score (mcl_impl.hip), whose particle set is one "rig" of up to 4096.
-template <int NT, int SPLIT>
-__device__ __forceinline__ void track_score_block(const FrameDesc* __restrict__ frames,
-                                                  const uint32_t* __restrict__ mbits, size_t bstride,
-                                                  const Landmarks& lmk, const Xf* __restrict__ c2w,
-                                                  const PoseF* __restrict__ pf, long long* __restrict__ sums,
-                                                  int32_t* __restrict__ cnt, size_t t0, int C, int f, int cam,
-                                                  int chunk, int np) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  constexpr int kW = NT / 64, kPP = kW / SPLIT;  // particles per block (one task per wave)
-  static_assert(kW % SPLIT == 0 && kPP >= 1 && 64 * kScrUnroll * SPLIT >= 768, "one register trip per slice");
-  const FrameDesc fd = frames[f];
-  const int W = fd.w, H = fd.h;
-  const int nl = lmk.nw + lmk.nr + lmk.ng;
-  __shared__ float4 lmf[768];
-  __shared__ Xf Pc[kPP];
-  __shared__ PoseF Pf[kPP];
-  __shared__ unsigned long long Ps[kPP];
-  __shared__ int32_t Pn[kPP];
-  __shared__ uint32_t uqe[kPfQueue];
-  __shared__ int32_t uqn;
-  const int j0 = chunk * kPP, nj = max(0, min(kPP, np - j0));
-  for (int i = tid; i < nl; i += NT) lmf[i] = lmk.xyzf[i];
-  if (tid < nj) {
-    const size_t t = t0 + (size_t)(j0 + tid) * C + cam;
-    Pc[tid] = c2w[t];
-    Pf[tid] = pf[t];
-    Ps[tid] = 0;
-    Pn[tid] = 0;
-  }
-  if (tid == 0) uqn = 0;
-  __syncthreads();
-  const UQueue q{uqe, &uqn, kPfQueue};
-  const MaskBits mask{mbits + (size_t)f * bstride, bits::tiled_rows(H), W};
-  WaveLms<kScrUnroll> wl;
-  {
-    const int h = wave % SPLIT;
-    wl.load(lmf, nl * h / SPLIT, nl * (h + 1) / SPLIT);
-  }
-  for (int task = __builtin_amdgcn_readfirstlane(wave); task < nj * SPLIT; task += kW) {
-    const int j = task / SPLIT;  // task % SPLIT == wave % SPLIT: the wave's resident slice
-    long long sum;
-    int cnt;
-    wl.sums(Pf[j], fd.scam, W, H, fd.bgr, mask, q, j, &Pc[j], lmk.xyz, &frames[f].cam, sum, cnt);
-    if (lane == 0) {
-      atomicAdd(&Ps[j], (unsigned long long)sum);
-      atomicAdd(&Pn[j], cnt);
-    }
-  }
-  __syncthreads();
-  block_drain(q, lmk.xyz, &frames[f].cam, W, H, fd.bgr, mask, [&](int t) -> const Xf& { return Pc[t]; },
-              [&](int t, int e) {
-                atomicAdd(&Ps[t], (unsigned long long)e);
-                atomicAdd(&Pn[t], 1);
-              });
-  __syncthreads();
-  if (tid < nj) {
-    const size_t t = t0 + (size_t)(j0 + tid) * C + cam;
-    sums[t] = (long long)Ps[tid];
-    cnt[t] = Pn[tid];
-  }
-}
+// Pass `pass` of every rig on every camera: block (chunk, camera, rig) scores
+// particles [chunk * kTrackPP, ...) of the pass (np of them: 1 for the seed)
+// with pose_score_block (kernels.hip; shared with k_mcl_score, whose particle
+// set is one "rig" of up to 4096).
 template <int NT, int SPLIT>
 __global__ __launch_bounds__(NT) void k_track_score(const FrameDesc* __restrict__ frames,
                                                     const uint32_t* __restrict__ mbits, size_t bstride, Landmarks lmk,
                                                     TrackArgs a, int pass, int np) {
   const int chunk = blockIdx.x, cam = blockIdx.y, rig = blockIdx.z;
-  track_score_block<NT, SPLIT>(frames, mbits, bstride, lmk, a.c2w, a.pf, a.sums, a.cnt,
+  pose_score_block<NT, SPLIT>(frames, mbits, bstride, lmk, a.c2w, a.pf, a.sums, a.cnt,
                                (size_t)pass * a.pass_tasks + (size_t)rig * a.P * a.C, a.C, rig * a.C + cam, cam, chunk,
                                np);
 }

@@ -202,6 +202,46 @@ def test_replay_from_the_record(mantis, scene, N, Cn):
     assert N == 1 or np.any(rec["L_before"] != 0.0)
 
 
+def test_screen_off_equals_screen_on(mantis, scene, landmark_map):
+    """A context created with MANTIS_SCREEN=0 sends every landmark of every
+    (particle, camera) through the exact fallback -- the scoring blocks'
+    queues overflow, so the in-place path runs, then the drains -- and must
+    record the same integer sums and counts and return the same result
+    records from the same set and RNG state. 13 particles: a full chunk of 8
+    and a tail of 5 per camera."""
+    import os
+
+    import mantis_amd as M
+
+    N, Cn = 13, 2
+    old = os.environ.get("MANTIS_SCREEN")
+    os.environ["MANTIS_SCREEN"] = "0"
+    try:
+        mx = M.Mantis(max_cams=8, max_width=W, max_height=H)
+    finally:
+        if old is None:
+            del os.environ["MANTIS_SCREEN"]
+        else:
+            os.environ["MANTIS_SCREEN"] = old
+    try:
+        mx.set_map(*landmark_map)
+        T0 = _cloud(scene, N, 100 + N)
+        got = []
+        for m in (mx, mantis):
+            m.rng_state = 1
+            m.prior_pose = None
+            m.mcl_init_particles(T0, sigma_rot=0.01, sigma_t=0.005, tau=TAU, resample_frac=2.0, record=1)
+            out, mo = m.mcl_step(_images(scene, CAMS[:Cn]))
+            got.append((bytes(out), bytes(mo), m.mcl_record(), m.rng_state))
+        (ox, mox, rx, sx), (os_, mos, rs, ss) = got
+        assert rx["sums"].shape == rs["sums"].shape == (N, Cn)
+        assert np.array_equal(rx["sums"], rs["sums"]) and np.array_equal(rx["counts"], rs["counts"])
+        assert np.array_equal(rx["c2w"], rs["c2w"]) and np.array_equal(rx["ancestors"], rs["ancestors"])
+        assert ox == os_ and mox == mos and sx == ss
+    finally:
+        mx.close()
+
+
 def test_carry_over(mantis, scene):
     """Two steps on the same frames, no resampling, no diffusion, no motion."""
     N = 33

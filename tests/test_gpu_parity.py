@@ -622,25 +622,33 @@ def test_screen_off_equals_screen_on(frames, landmark_map):
     exact FP64 path: a context created with MANTIS_SCREEN=0 sends every
     landmark through the exact fallback (the block queues overflow, so the
     in-place path runs too, then the drains); every error, count and decision
-    must be identical, in the pipeline (init / particle filter / shifts) and in
-    the standalone scorer (k_score_api, with and without a mask)."""
+    must be identical, in the pipeline (init / particle filter / shifts) --
+    the split small-batch kernels, then the throughput kernels forced on the
+    same frames (MANTIS_FC_SMALL_FRAMES=0: k_score_pf with the init and the
+    shifts inside, mask in LDS, and with MANTIS_PF_MASK_GLOBAL=1 the global
+    mask) -- in the standalone scorer (k_score_api, with and without a mask)
+    and in the dense batch (k_score_api_batch: blocks of 64 hypotheses, a
+    tail block, with and without a mask)."""
     import os
 
     import mantis_amd as M
 
     K, D = synth.intrinsics()
     imgs = [M.make_image(fr[0], K, D) for fr in frames[:4]]
-    old = os.environ.get("MANTIS_SCREEN")
-    os.environ["MANTIS_SCREEN"] = "0"
-    try:
-        mx = M.Mantis(max_cams=4, max_width=1280, max_height=720)
-    finally:
-        if old is None:
-            del os.environ["MANTIS_SCREEN"]
-        else:
-            os.environ["MANTIS_SCREEN"] = old
-    ms = M.Mantis(max_cams=4, max_width=1280, max_height=720)
-    try:
+
+    def ctx(env):
+        saved = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            return M.Mantis(max_cams=4, max_width=1280, max_height=720)
+        finally:
+            for k, v in saved.items():
+                if v is None:
+                    del os.environ[k]
+                else:
+                    os.environ[k] = v
+
+    def pipeline(mx, ms):
         for m in (mx, ms):
             m.set_map(*landmark_map)
             m.rng_state = 1
@@ -658,16 +666,56 @@ def test_screen_off_equals_screen_on(frames, landmark_map):
             assert gx.yaw_best == gs.yaw_best and gx.publish == gs.publish
             assert list(cx[f].position) == list(cs[f].position)
         assert mx.rng_state == ms.rng_state
+
+    for env in ({"MANTIS_FC_SMALL_FRAMES": "0"}, {"MANTIS_FC_SMALL_FRAMES": "0", "MANTIS_PF_MASK_GLOBAL": "1"}):
+        mx, ms = ctx(dict(env, MANTIS_SCREEN="0")), ctx(env)
+        try:
+            assert M.lib().mantis_small_batch_frames(ms.h) < len(imgs), "the throughput kernels must run"
+            pipeline(mx, ms)
+        finally:
+            mx.close()
+            ms.close()
+    mx, ms = ctx({"MANTIS_SCREEN": "0"}), ctx({})
+    ptrs = []
+    try:
+        assert M.lib().mantis_small_batch_frames(ms.h) >= len(imgs), "the split small-batch kernels must run"
+        pipeline(mx, ms)
         rng = np.random.default_rng(5)
         img, R, pos = frames[0]
         c2w = [synth.truth_c2w(R @ synth.rot_z(rng.normal() * 0.05), pos + rng.normal(size=3) * 0.02)
                for _ in range(300)]
-        c2w = np.array(c2w)
-        for mask in (None, ms.masks(imgs[0])[1]):
-            ex, nx = mx.score(imgs[0], c2w, fast=True, mask=mask)
-            es, ns = ms.score(imgs[0], c2w, fast=True, mask=mask)
+        c2w = np.ascontiguousarray(np.array(c2w), np.float64).reshape(-1, 12)
+        mask = ms.masks(imgs[0])[1]
+        per = {}
+        for key, mk in (("none", None), ("mask", mask)):
+            ex, nx = mx.score(imgs[0], c2w, fast=True, mask=mk)
+            es, ns = ms.score(imgs[0], c2w, fast=True, mask=mk)
             assert np.array_equal(nx, ns) and np.array_equal(ex, es)
+            per[key] = es
+        # the dense batch: the 300 hypotheses as four jobs on the one frame (two
+        # full blocks and a tail, a block and a tail, one full block, one
+        # partial block). The batch entry returns each job's (lowest error,
+        # first index): equal with the screen off and on, and the first
+        # minimum of the per-hypothesis errors above.
+        cuts = [0, 130, 200, 264, 300]
+        d_h = ms.device_alloc(c2w.nbytes)
+        ptrs.append(d_h)
+        ms.h2d(d_h, c2w)
+        d_m = ms.device_alloc(mask.nbytes)
+        ptrs.append(d_m)
+        ms.h2d(d_m, np.ascontiguousarray(mask, np.uint8))
+        hp = [d_h + 12 * 8 * lo for lo in cuts[:-1]]
+        ns_ = [hi - lo for lo, hi in zip(cuts[:-1], cuts[1:])]
+        for key, mp in (("none", None), ("mask", [d_m] * 4)):
+            bx = mx.score_argmin_batch([imgs[0]] * 4, hp, ns_, cuts[:-1], False, mp)
+            bs = ms.score_argmin_batch([imgs[0]] * 4, hp, ns_, cuts[:-1], False, mp)
+            assert bx == bs, key
+            for k, (lo, hi) in enumerate(zip(cuts[:-1], cuts[1:])):
+                i = lo + int(np.argmin(per[key][lo:hi]))
+                assert bs[k] == (per[key][i], i), (key, k)
     finally:
+        for p_ in ptrs:
+            ms.device_free(p_)
         mx.close()
         ms.close()
 

@@ -544,9 +544,11 @@ def test_dense_config5_full_grid_8_shards(m720, landmark_map):
 def test_pf_mask_lds_and_global_paths_agree(landmark_map):
     """k_score_pf reads the clean mask from an LDS copy of the frame's tiled
     plane when it fits (720p) and through the L1 otherwise
-    (MANTIS_PF_MASK_GLOBAL=1 forces that path); both block shapes (the
-    small-batch 1024-thread one and the large-batch 640-thread one, chosen by
-    MANTIS_TRACE_LDS_FRAMES) must give bit-identical frame results."""
+    (MANTIS_PF_MASK_GLOBAL=1 forces that path); both must give bit-identical
+    frame results and frame records. MANTIS_FC_SMALL_FRAMES=0 puts the
+    4-frame batch on the throughput kernels, so that k_score_pf is what runs
+    (a small batch takes k_score_pf_part, which always reads the global mask);
+    run with either border-walk kernel (MANTIS_TRACE_LDS_FRAMES)."""
     import os
 
     import mantis_amd as M
@@ -573,15 +575,18 @@ def test_pf_mask_lds_and_global_paths_agree(landmark_map):
             m.set_map(*landmark_map)
             m.rng_state = 1
             _, cams = m.process(frames)
-            return [(c.reason, c.publish, c.pf_error, tuple(c.position), tuple(c.orientation_xyzw)) for c in cams]
+            assert M.lib().mantis_small_batch_frames(m.h) < len(frames), "the throughput kernels must run"
+            return ([(c.reason, c.publish, c.pf_error, tuple(c.position), tuple(c.orientation_xyzw)) for c in cams],
+                    [bytes(m.frame_debug(f)) for f in range(len(frames))])
         finally:
             m.close()
 
     for small in ("64", "0"):
-        lds = run({"MANTIS_TRACE_LDS_FRAMES": small})
-        glob = run({"MANTIS_TRACE_LDS_FRAMES": small, "MANTIS_PF_MASK_GLOBAL": "1"})
-        assert lds == glob, small
-        assert any(r[0] >= 0 for r in lds)
+        lds = run({"MANTIS_FC_SMALL_FRAMES": "0", "MANTIS_TRACE_LDS_FRAMES": small})
+        glob = run({"MANTIS_FC_SMALL_FRAMES": "0", "MANTIS_TRACE_LDS_FRAMES": small, "MANTIS_PF_MASK_GLOBAL": "1"})
+        assert lds[0] == glob[0], small
+        assert lds[1] == glob[1], small
+        assert any(r[0] >= 0 for r in lds[0])
 
 
 def test_dense_batch_matches_per_frame(m720, landmark_map):

@@ -174,6 +174,46 @@ def test_shapes_that_break_loops(mantis, scene, P, cams, I):
             mantis.track_record(0, 1)
 
 
+def test_screen_off_equals_screen_on(mantis, scene, landmark_map):
+    """A context created with MANTIS_SCREEN=0 sends every landmark of every
+    (particle, camera) through the exact fallback -- the scoring blocks'
+    queues overflow, so the in-place path runs, then the drains -- and must
+    record the same integer sums and counts in every pass and return the same
+    result record from the same RNG state. 11 particles: a full chunk of 8
+    and a tail of 3 per camera."""
+    import os
+
+    import mantis_amd as M
+
+    cams, P, I = (0, 3, 5), 11, 2
+    old = os.environ.get("MANTIS_SCREEN")
+    os.environ["MANTIS_SCREEN"] = "0"
+    try:
+        mx = M.Mantis(max_cams=8, max_width=W, max_height=H)
+    finally:
+        if old is None:
+            del os.environ["MANTIS_SCREEN"]
+        else:
+            os.environ["MANTIS_SCREEN"] = old
+    try:
+        mx.set_map(*landmark_map)
+        pred = _shift(scene["Twb"][0])
+        got = []
+        for m in (mx, mantis):
+            m.rng_state = 1
+            res = m.track_batch(_images(scene, 0, cams), 1, pred, particles=P, iterations=I, record=1)[0]
+            got.append((bytes(res), [m.track_record(0, k) for k in (-1, 1, 2)], m.rng_state))
+        (rx, px, sx), (rs, ps, ss) = got
+        for k, (a, b) in enumerate(zip(px, ps)):
+            assert a[2].shape == b[2].shape == ((1 if k == 0 else P), len(cams))
+            assert np.array_equal(a[2], b[2]), f"pass {k}: sums"
+            assert np.array_equal(a[3], b[3]), f"pass {k}: counts"
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), f"pass {k}: poses"
+        assert rx == rs and sx == ss
+    finally:
+        mx.close()
+
+
 def test_ties(mantis, scene):
     """sigma 0: every particle equals the current pose, none is strictly better."""
     pred = _shift(scene["Twb"][0])

@@ -19,6 +19,8 @@ def _hc():
     vp = C.c_void_p
     L.hc_track_pool.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     L.hc_track_pool.restype = None
+    L.hc_track_error_of.argtypes = [C.c_int64, C.c_int32]
+    L.hc_track_error_of.restype = C.c_double
     L.hc_track_pick.argtypes = [vp, C.c_int, C.c_double]
     L.hc_track_pick.restype = C.c_int
     L.hc_track_gate.argtypes = [C.c_double, C.c_int32, C.c_int32, C.c_double]
@@ -100,6 +102,18 @@ def test_pool_matches_numpy():
     counts = np.array([[768, 768], [768, 0]], np.int32)
     e, n = pool(sums, counts)
     assert np.array_equal(e, np_pool(sums, counts)[0]) and list(n) == [1536, 768]
+
+
+def test_error_of_is_pool_with_one_camera():
+    """The single scorers' error (track::error_of: the pipeline's init, particle
+    filter and shifts, the standalone scorer) is the pooled error of one camera."""
+    cases = [(0, 0), (5, 0), (0, 1), (3 * 255 * 255, 1), (123456789, 700), (3 * 255 * 255 * 768, 768),
+             (1, 3), ((1 << 53) + 1, 7), (10, -1)]
+    for s, n in cases:
+        e = _hc().hc_track_error_of(s, n)
+        pe, pn = pool([[s]], [[n]])
+        assert e == pe[0] and pn[0] == n
+        assert e == (DBL_MAX if n <= 0 else float(np.float64(s) / (np.float64(n) * 1.1)))
 
 
 def test_all_blind_cameras():

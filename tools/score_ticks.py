@@ -1,7 +1,8 @@
 """Phase times of k_score_final per frame (a library built with
 -DMK_SCORE_TICKS, MANTIS_AMD_LIB): one context, one batch of bench rigs;
 median / p90 of each phase over the frames that reach the particle filter.
-Phases: shift tasks, unsure drain, top-20, yaw-set build, COLOR windows, publish.
+Phases: shift poses and errors (their sums come from k_score_pf or
+k_score_shift_part), top-20, yaw-set build, COLOR windows, publish.
 With "pf" (a library built with -DMK_SCORE_TICKS=2): k_score_pf (the particle filter)'s
 phases summed over its iterations: mask staging, particle poses, screened
 tasks, unsure drain, per-particle sums, argmin.
@@ -58,12 +59,13 @@ def main(rigs, pf=False, color=False):
         d = tk
         tk = np.cumsum(tk, axis=1)
         names = ["staging", "particles", "tasks", "drain", "sums", "argmin"]
-    else:
+    else:  # phase ends in slots 1 .. 5 (slot 0 is not written)
+        tk = tk[:, 1:6]
         d = np.diff(np.concatenate([np.zeros((len(tk), 1)), tk], 1), axis=1)
-        names = ["shift tasks", "drain", "top-20", "yaw build", "COLOR", "publish"]
+        names = ["shift errors", "top-20", "yaw build", "COLOR", "publish"]
     for j, nm in enumerate(names):
         print(f"{nm:12s} median {np.median(d[:, j]):8.1f} us  p90 {np.percentile(d[:, j], 90):8.1f} us")
-    print(f"total        median {np.median(tk[:, 5]):8.1f} us over {len(tk)} frames")
+    print(f"total        median {np.median(tk[:, -1]):8.1f} us over {len(tk)} frames")
     m.close()
 
 

@@ -1,5 +1,5 @@
 // Stand-alone check of the rig-tracking rules (mantis_amd/csrc/mk_track.h:
-// pool, pick, gate, particle) on the cases tests/test_track_host.py runs
+// pool / error_of, pick, gate, particle) on the cases tests/test_track_host.py runs
 // through the host helper library, as a program of its own so that it can be
 // built with sanitizers and run directly:
 //   g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined \
@@ -60,8 +60,10 @@ int main() {
       int32_t a, b;
       const double e = t::pool(s.data(), n.data(), sh[1], &a), r = ref_pool(s, n, &b);
       CHECK(e == r && a == b);
+      CHECK(sh[1] != 1 || t::error_of(s[0], n[0]) == e);  // one camera: the single scorers' error
     }
   }
+  CHECK(t::error_of(0, 0) == DBL_MAX && t::error_of(5, 0) == DBL_MAX && t::error_of(0, 1) == 0.0);
   {  // all-blind cameras: DBL_MAX, no pick, not tracked
     std::vector<long long> s(4, 0);
     std::vector<int32_t> n(4, 0);
