@@ -699,6 +699,117 @@ mantis_status mantis_mcl_get_color_record(void* ctx, int64_t* csums, int32_t* cc
  * pointer. */
 mantis_status mantis_mcl_modes_color(void* ctx, double* color_error /*8*/, int32_t* color_n /*8*/);
 
+/* ---- Line refinement: Gauss-Newton on the grid lines from a pose prior ----
+ * A continuous refinement that needs no detection and reads the raw BGR
+ * frames only (no image stage runs, nothing is drawn: the cv::RNG state is
+ * untouched). MANTIS_ABI_VERSION stays 5: callers find these entries by name
+ * and check the struct sizes through mantis_refine_sizes.
+ *
+ * Landmarks: all n = nw + nr + ng in map order; target colour by set, BGR:
+ * WHITE (255, 255, 255), RED (50, 85, 255), GREEN (50, 255, 85).
+ * Line flags (host, cached until the next mantis_set_map or another
+ * landmark_pitch): bit 0 of landmark i is set iff some landmark j != i lies at
+ * X_i +- (pitch, 0, 0), every coordinate agreeing within 1e-6; bit 1 the same
+ * along y. A candidate has flags exactly 1 (tangent e = x) or exactly 2
+ * (e = y); intersections (and the map's duplicated intersection landmarks)
+ * have both and are never used. Candidates are numbered in ascending landmark
+ * order (n_cand of them).
+ *
+ * One observation of (base pose T, camera c, candidate i), R_cb / t_cb =
+ * inverse(T_base_cam_c):
+ *  1. q = R_wb^T (X - t_wb), p = R_cb q + t_cb; p_z <= 0: code 1.
+ *  2. iz = 1 / p_z, m0 = (p_x iz, p_y iz), Jpi = [[iz, 0, -p_x iz^2], [0, iz, -p_y iz^2]].
+ *  3. t = Jpi (R_cb R_wb^T e); |t| < 1e-12: code 2. th = t / |t|, nh = (-th_y, th_x).
+ *  4. samples k = -R .. R, step s = 1 / fx (the float-rounded K): (u_k, v_k) =
+ *     distort(m0 + (k s) nh, 1), x_k = cvRound(u_k), y_k = cvRound(v_k); a
+ *     sample that is not finite or has x_k outside [0, W) or y_k outside
+ *     [0, H): code 3.
+ *  5. at pixel (x_k, y_k) of the raw frame: d2_k = sum_ch (pix - target)^2,
+ *     w_k = max(0, white_thresh - d2_k), int32.
+ *  6. w_-R > 0 or w_R > 0: code 4 (the line must lie strictly inside the window).
+ *  7. Sw = sum w_k, Skw = sum k w_k (exact int32); Sw < min_weight: code 5.
+ *  8. else code 0: d = ((double)Skw / (double)Sw) s, residual r = -d,
+ *     h = (nh^T Jpi) R_cb, row J = [-h | h [q]x].
+ * The first failing test decides the code; a row with a non-zero code is seven
+ * zeros (and Sw = Skw = 0 for codes 1..3). Row slot = c n_cand + candidate;
+ * no compaction (zero rows add exact zeros).
+ *
+ * Pass k = 0 .. I - 1 at pose T_k: the observations; acc28 = the upper
+ * triangle of J^T J (21), J^T r (6), r^T r (1); n_obs[k] = the code-0 rows,
+ * rms[k] = sqrt(r^T r / n_obs) (normalized image units; x fx ~ pixels; 0 when
+ * n_obs = 0); n_obs < min_obs: status STARVED (1), stop; (J^T J + lambda I)
+ * not positive definite: status SINGULAR (2), stop; else T_k+1 = T_k
+ * Exp(delta[k]) (right perturbation, translation then rotation vector).
+ * After the loop one more observation pass at the last pose gives the final
+ * n_obs, rms and acc28 (I + 1 passes; I = 0 returns the pose bit for bit).
+ * iterations_run = the steps taken; the final figures are n_obs /
+ * rms[iterations_run] (a rig that stopped keeps those of the pass that stopped
+ * it: same pose, same observations). Entries past it are 0.
+ * refined = status OK && final n_obs >= min_obs && (max_rms <= 0 || final rms
+ * <= max_rms). covariance (host): sigma^2 = r^T r / (n_obs - 6), Cov_delta =
+ * sigma^2 (J^T J)^-1 by Cholesky, translation block turned to the world frame
+ * (B Cov B^T, B = diag(R_wb, I)); order x, y, z, rot-x, rot-y, rot-z,
+ * row-major. A non-PD J^T J or n_obs <= 6: zeros and refined = 0. */
+typedef struct mantis_refine_params {
+  int32_t struct_size;     /* sizeof(mantis_refine_params) */
+  int32_t iterations;      /* I, 0..10 */
+  int32_t half_window;     /* R, 1..15 */
+  int32_t white_thresh;    /* 1..195075 */
+  int32_t min_weight;      /* >= 1 */
+  int32_t min_obs;         /* >= 6 */
+  double lambda;           /* >= 0 */
+  double landmark_pitch;   /* > 0 */
+  double max_rms;          /* gate on the final rms; <= 0 means none */
+  int32_t record;          /* 1 = keep every pass's rows (mantis_get_refine_record) */
+  int32_t pad;
+} mantis_refine_params;
+/* 4 / 12 / 12288 (3 x 64^2) / 24576 / 12 / 0 / 0.08 / 0 / 0 */
+void mantis_default_refine_params(mantis_refine_params* p);
+
+typedef struct mantis_refine_result {
+  int32_t status, refined, iterations_run, n_cand; /* status: 0 OK, 1 STARVED, 2 SINGULAR */
+  double T_w_b[16];        /* refined base pose, row-major */
+  int32_t n_obs[11];       /* per pass */
+  int32_t pad;
+  double rms[11];
+  double delta[10][6];
+  double covariance[36];
+} mantis_refine_result;
+/* sizeof(mantis_refine_params), sizeof(mantis_refine_result) (host only) */
+void mantis_refine_sizes(int32_t* params_bytes, int32_t* result_bytes);
+
+/* The cached line flags of the current map at `pitch` (rule above): n must be
+ * nw + nr + ng, flags_out gets one byte per landmark. Host only.
+ * MANTIS_ERR_ARG: no map, pitch not finite and > 0, n mismatch, null. */
+mantis_status mantis_refine_line_flags(void* ctx, double pitch, uint8_t* flags_out, int32_t n);
+
+/* n_rigs rigs of cams_per_rig cameras (cams[r * cams_per_rig + c], one frame
+ * size; host or device frames, any step_bytes >= 3 W), rig r refined from
+ * T_w_b_in[r] (n_rigs x 16, row-major) by the rule above. Argument limits as
+ * mantis_track_batch. MANTIS_ERR_ARG (nothing launched; mantis_last_error
+ * names the field): no map, n_rigs x cams_per_rig > max_cams, cams_per_rig >
+ * 8, frames of different sizes, a parameter outside its range. Device work:
+ * 2 (I + 1) launches on the context stream (k_refine_obs, k_refine_step per
+ * pass), then one copy of the results. */
+mantis_status mantis_refine_batch(void* ctx, const mantis_image* cams, int32_t n_rigs, int32_t cams_per_rig,
+                                  const double* T_w_b_in, const mantis_refine_params* p, mantis_refine_result* out);
+/* One rig from the context's prior: start = prior * Transform(delta_quat,
+ * delta_pos), the prior itself when motion is NULL or unset, exactly as
+ * mantis_track forms its prediction. MANTIS_ERR_STATE without a prior.
+ * Refined: the prior becomes T_w_b and out is a published rig (publish = 1,
+ * getRotation quaternion, the covariance above, weight = final rms,
+ * num_particles = final n_obs). Not refined: publish = 0, the prior stays.
+ * rout (nullable) gets the details. */
+mantis_status mantis_refine(void* ctx, const mantis_image* cams, int32_t n_cams, const mantis_motion* motion,
+                            const mantis_refine_params* p, mantis_result* out, mantis_refine_result* rout);
+/* Record of rig `rig`, pass 0 .. iterations_run of that rig, of the last
+ * refine call made with record = 1; each pointer nullable: T_w_b (16) the
+ * pose the pass observed at; per slot (C x n_cand, slot = c n_cand +
+ * candidate) codes, Sw, Skw and rows (7 doubles each); acc28 of the pass.
+ * MANTIS_ERR_STATE: no such record. MANTIS_ERR_ARG: rig or pass out of range. */
+mantis_status mantis_get_refine_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, int32_t* codes,
+                                       int32_t* Sw, int32_t* Skw, double* rows, double* acc28);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,19 @@ class MantisMclColorParams(C.Structure):
                 ("color_miss", C.c_double), ("min_color_projections", C.c_int32), ("pad", C.c_int32)]
 
 
+class MantisRefineParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("half_window", C.c_int32),
+                ("white_thresh", C.c_int32), ("min_weight", C.c_int32), ("min_obs", C.c_int32),
+                ("lambda_", C.c_double), ("landmark_pitch", C.c_double), ("max_rms", C.c_double),
+                ("record", C.c_int32), ("pad", C.c_int32)]
+
+
+class MantisRefineResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("refined", C.c_int32), ("iterations_run", C.c_int32), ("n_cand", C.c_int32),
+                ("T_w_b", C.c_double * 16), ("n_obs", C.c_int32 * 11), ("pad", C.c_int32), ("rms", C.c_double * 11),
+                ("delta", (C.c_double * 6) * 10), ("covariance", C.c_double * 36)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -224,6 +237,15 @@ _SIGS = {
     "mantis_mcl_set_color": (C.c_int, [C.c_void_p, C.POINTER(MantisMclColorParams)]),
     "mantis_mcl_get_color_record": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.POINTER(C.c_int32)] * 2),
     "mantis_mcl_modes_color": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mantis_default_refine_params": (None, [C.POINTER(MantisRefineParams)]),
+    "mantis_refine_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_refine_line_flags": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_int32]),
+    "mantis_refine_batch": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32, C.c_void_p,
+                                      C.POINTER(MantisRefineParams), C.POINTER(MantisRefineResult)]),
+    "mantis_refine": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.POINTER(MantisMotion),
+                                C.POINTER(MantisRefineParams), C.POINTER(MantisResult),
+                                C.POINTER(MantisRefineResult)]),
+    "mantis_get_refine_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
 }
 
 
@@ -503,6 +525,82 @@ class Mantis:
         P = npart.value
         return (T[:P].reshape(P, 4, 4).copy(), c2w[: P * Cn * 12].reshape(P, Cn, 12).copy(),
                 sums[: P * Cn].reshape(P, Cn).copy(), cnt[: P * Cn].reshape(P, Cn).copy())
+
+    # line refinement (mantis_refine*, include/mantis.h) ----------------------
+    def refine_params(self, **params):
+        """mantis_default_refine_params, then the overrides (`lambda_` is the C field `lambda`)."""
+        p = MantisRefineParams()
+        lib().mantis_default_refine_params(C.byref(p))
+        for k, v in params.items():
+            if k not in dict(MantisRefineParams._fields_) or k == "struct_size":
+                raise TypeError(f"refine: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def refine_batch(self, images, rigs, T_in, **params):
+        """mantis_refine_batch: `rigs` rigs (images rig-major) refined on the
+        grid lines from the base poses T_in (rigs x 4 x 4); returns the rigs'
+        MantisRefineResult records."""
+        n = len(images)
+        assert rigs > 0 and n % rigs == 0
+        cams = (MantisImage * n)(*images)
+        T = np.ascontiguousarray(T_in, np.float64).reshape(-1)
+        assert T.size == 16 * rigs
+        p = self.refine_params(**params)
+        out = (MantisRefineResult * rigs)()
+        self._chk(lib().mantis_refine_batch(self.h, cams, rigs, n // rigs, T.ctypes.data, C.byref(p), out),
+                  "refine_batch")
+        self._refine_slots = (n // rigs) * out[0].n_cand
+        return list(out)
+
+    def refine(self, images, delta_pos=None, delta_quat_xyzw=None, **params):
+        """mantis_refine: one rig from the context's prior pose and an optional
+        mantisService motion; returns (MantisResult, MantisRefineResult).
+        result.publish == 0: not refined, fall back to process_motion()."""
+        n = len(images)
+        cams = (MantisImage * n)(*images)
+        mo = None
+        if delta_pos is not None:
+            mo = MantisMotion()
+            for i in range(3):
+                mo.delta_pos[i] = delta_pos[i]
+            for i in range(4):
+                mo.delta_quat_xyzw[i] = delta_quat_xyzw[i]
+        p = self.refine_params(**params)
+        out = MantisResult()
+        rout = MantisRefineResult()
+        st = lib().mantis_refine(self.h, cams, n, None if mo is None else C.byref(mo), C.byref(p), C.byref(out),
+                                 C.byref(rout))
+        self._chk(st, "refine")
+        self._refine_slots = n * rout.n_cand
+        return out, rout
+
+    def refine_record(self, rig, pass_):
+        """Pass `pass_` (0 .. the rig's iterations_run) of rig `rig` of the last
+        refine call made with record=1 (mantis_get_refine_record): (T_w_b
+        [4, 4], codes, Sw, Skw [slots] int32, rows [slots, 7], acc28 [28]);
+        slot = camera x n_cand + candidate."""
+        ns = getattr(self, "_refine_slots", None)
+        if ns is None:
+            raise MantisError("refine_record: no refine call on this context")
+        T = np.zeros((4, 4))
+        codes = np.zeros(ns, np.int32)
+        Sw = np.zeros(ns, np.int32)
+        Skw = np.zeros(ns, np.int32)
+        rows = np.zeros((ns, 7))
+        acc = np.zeros(28)
+        self._chk(lib().mantis_get_refine_record(self.h, rig, pass_, T.ctypes.data, codes.ctypes.data, Sw.ctypes.data,
+                                                 Skw.ctypes.data, rows.ctypes.data, acc.ctypes.data),
+                  "get_refine_record")
+        return T, codes, Sw, Skw, rows, acc
+
+    def line_flags(self, pitch=0.08):
+        """mantis_refine_line_flags: one byte per landmark of the current map
+        (bit 0: a neighbour at +- pitch along x, bit 1: along y)."""
+        n = sum(len(a) for a in self._map)
+        f = np.zeros(n, np.uint8)
+        self._chk(lib().mantis_refine_line_flags(self.h, float(pitch), f.ctypes.data, n), "refine_line_flags")
+        return f
 
     # Monte Carlo localization (mantis_mcl_*, include/mantis.h) ---------------
     def mcl_params(self, **params):

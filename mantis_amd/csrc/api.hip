@@ -326,6 +326,24 @@ struct Ctx {
     int color_cap = 0;                      // particles the colour buffers hold
     int rec_color = 0, rec_color_min = 0;   // the last step's enable and min_color_projections
   } mcl;
+  // line refinement (refine_impl.hip): the map's host copy and the line flags
+  // cached on it (until the next mantis_set_map or another pitch), workspaces
+  // grown to the largest call, and the last call's shape (mantis_get_refine_record)
+  std::vector<double> h_lm;  // the map as mantis_set_map got it: n x 3
+  struct Refine {
+    std::vector<uint8_t> flags;
+    double pitch = 0;  // of `flags`; 0 = none cached
+    int n_cand = 0;
+    int32_t* d_cand = nullptr;  // n_cand: landmark | axis << 16
+    int cand_cap = 0;
+    void *d_gncam = nullptr, *d_state = nullptr, *h_state = nullptr;  // per camera; per rig (h: pinned)
+    double *d_recT = nullptr, *d_recAcc = nullptr;                   // [pass][rig][16] / [28]
+    int rig_cap = 0, cam_cap = 0;
+    void* d_slots = nullptr;  // [pass (record) or one][rig][C n_cand]
+    size_t slot_cap = 0;
+    int rigs = 0, C = 0, I = 0, record = 0, cands = 0;  // the last call
+    std::vector<int32_t> runs;                          // its rigs' iterations_run
+  } rf;
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1365,6 +1383,10 @@ mantis_status mantis_destroy(void* ctx) {
                    c->mcl.d_csums, c->mcl.d_ccnt, c->mcl.d_Ec, c->mcl.d_charge};
   for (void* p : mptrs)
     if (p) (void)hipFree(p);
+  void* rptrs[] = {c->rf.d_cand, c->rf.d_gncam, c->rf.d_state, c->rf.d_recT, c->rf.d_recAcc, c->rf.d_slots};
+  for (void* p : rptrs)
+    if (p) (void)hipFree(p);
+  if (c->rf.h_state) (void)hipHostFree(c->rf.h_state);
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
                    c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes};
@@ -1411,6 +1433,9 @@ mantis_status mantis_set_map(void* ctx, const double* white, int32_t nw, const d
   c->nw = nw;
   c->nr = nr;
   c->ng = ng;
+  c->h_lm = all;
+  c->rf.pitch = 0;  // the line flags of the previous map go (refine_impl.hip)
+  c->rf.rigs = 0;
   return MANTIS_OK;
 }
 
@@ -2215,4 +2240,5 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "mcl_impl.hip"
 #include "mcl_modes_impl.hip"
 #include "mcl_color_impl.hip"
+#include "refine_impl.hip"
 #include "ros_wire.h"

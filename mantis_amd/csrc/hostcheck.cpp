@@ -19,6 +19,7 @@ static int g_jacobi_ff = 1;
 #include "mk_mcl.h"
 #include "mk_mcl_color.h"
 #include "mk_mcl_modes.h"
+#include "mk_refine.h"
 #include "mk_rpp.h"
 #include "mk_screen.h"
 #include "mk_shard.h"
@@ -542,5 +543,73 @@ void hc_mcl_color_fold(const double* L, const double* E, const int32_t* n_proj, 
   for (int j = 0; j < N; j++)
     L_out[j] = mk::mcl::log_weight_color(L[j], E[j], n_proj[j], min_projections, tau, charge[j]);
 }
+
+// Line refinement (mk_refine.h): the rules k_refine_obs / k_refine_step run.
+void hc_refine_flags(const double* X, int n, double pitch, uint8_t* flags) { mk::refine::line_flags(X, n, pitch, flags); }
+static mk::Cam hc_cam(const double* K, const double* D) {
+  return mk::Cam{(double)(float)K[0], (double)(float)K[4], (double)(float)K[2], (double)(float)K[5], {D[0], D[1], D[2], D[3]}};
+}
+// one pass for one camera (extrinsic T_base_cam) at base pose Twb over the
+// candidates of `flags`: per candidate the code, Sw, Skw, the 7 row doubles and
+// the tie-near flag (nullable); bgr: W x H, stride 3 W. Returns n_cand.
+int hc_refine_obs(const double* Twb, const double* Tbc, const double* K, const double* D, const uint8_t* bgr, int W,
+                  int H, const double* X, int nw, int nr, int ng, const uint8_t* flags, int R, int white_thresh,
+                  int min_weight, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, int32_t* tie) {
+  namespace rf = mk::refine;
+  const int n = nw + nr + ng;
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags, n, cand.data());
+  mk::GnCam gc;
+  rf::gncam_from(Tbc, gc);
+  const mk::Cam cm = hc_cam(K, D);
+  double Rt[9], t[3];
+  rf::pose_parts(Twb, Rt, t);
+  const rf::Window win{R, white_thresh, min_weight, 0};
+  for (int k = 0; k < nc; k++) {
+    const int i = cand[k] & 0xffff, axis = cand[k] >> 16;
+    int tg[3], near = 0;
+    rf::target_bgr(i, nw, nr, tg);
+    rf::Slot o;
+    rf::observe(Rt, t, gc, cm, bgr, W, H, X + 3 * i, axis, tg, win, o, &near);
+    codes[k] = o.code;
+    Sw[k] = o.Sw;
+    Skw[k] = o.Skw;
+    std::memcpy(rows + 7 * k, o.row, sizeof(o.row));
+    if (tie) tie[k] = near;
+  }
+  return nc;
+}
+// acc28 of n rows of 7 doubles, summed in row order
+void hc_refine_accumulate(const double* rows, int n, double* acc28) {
+  for (int e = 0; e < 28; e++) acc28[e] = 0.0;
+  for (int k = 0; k < n; k++) mk::refine::accumulate_row(rows + 7 * k, acc28);
+}
+// the whole iteration of one rig of C cameras (Tbc C x 16, K C x 9, D C x 4,
+// frames: C pointers to W x H frames of stride 3 W), rows summed in slot order
+void hc_refine_seq(const double* T_in, const double* Tbc, const double* K, const double* D, const uint8_t* const* frames,
+                   int C, int W, int H, const double* X, int nw, int nr, int ng, const mantis_refine_params* p,
+                   mantis_refine_result* out) {
+  namespace rf = mk::refine;
+  const int n = nw + nr + ng;
+  std::vector<uint8_t> flags(n > 0 ? n : 1);
+  rf::line_flags(X, n, p->landmark_pitch, flags.data());
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags.data(), n, cand.data());
+  std::vector<mk::GnCam> gc(C);
+  std::vector<mk::Cam> cm(C);
+  for (int c = 0; c < C; c++) {
+    rf::gncam_from(Tbc + 16 * c, gc[c]);
+    cm[c] = hc_cam(K + 9 * c, D + 4 * c);
+  }
+  rf::refine_seq(T_in, gc.data(), cm.data(), frames, C, W, H, X, nw, nr, cand.data(), nc, *p, *out, nullptr);
+}
+// gn_solve6 on its own (the step of a pass): returns 1 when solved
+int hc_gn_solve6(const double* acc28, double lambda, double* T, double* d6) { return mk::gn_solve6(acc28, lambda, T, d6) ? 1 : 0; }
+// the gate and the covariance (refine::conclude) of a result record with the last pass's acc28
+void hc_refine_conclude(const double* acc28, int min_obs, double max_rms, mantis_refine_result* R) {
+  mk::refine::conclude(acc28, min_obs, max_rms, *R);
+}
+int hc_sizeof_refine_params(void) { return (int)sizeof(mantis_refine_params); }
+int hc_sizeof_refine_result(void) { return (int)sizeof(mantis_refine_result); }
 
 }  // extern "C"
