@@ -810,6 +810,86 @@ mantis_status mantis_refine(void* ctx, const mantis_image* cams, int32_t n_cams,
 mantis_status mantis_get_refine_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, int32_t* codes,
                                        int32_t* Sw, int32_t* Skw, double* rows, double* acc28);
 
+/* ---- Monte Carlo localization: the modes refined on the grid lines ----
+ * A mode of mantis_mcl_modes is a weighted mean over a cell: its resolution is
+ * the particle spacing and its covariance the set's scatter. This call refines
+ * every mode of the last step on that step's frames by the line refinement
+ * above, unchanged, and on request moves each mode's particles rigidly so that
+ * the mode's mean sits on its refined pose. All addition: no other entry
+ * point, struct, kernel result or draw changes, MANTIS_ABI_VERSION stays 5
+ * (find the entries by name, check the sizes with mantis_mcl_refine_sizes).
+ *
+ * One call, in this order:
+ *  1. State and arguments. MANTIS_ERR_STATE where mantis_mcl_modes gives it (no
+ *     step since the last init or reset). MANTIS_ERR_ARG: a null pointer,
+ *     max_modes outside 1..8, apply not 0 or 1, and every parameter or frame
+ *     error of mantis_refine_batch taken with n_rigs = 1, cams_per_rig = n_cams
+ *     (mantis_last_error names the field): so n_cams <= min(8, max_cams), and
+ *     the number of modes never counts against max_cams. MANTIS_ERR_STATE also
+ *     for apply = 1 when an earlier apply = 1 call has moved particles since
+ *     the last step (a correction is applied once; apply = 0 stays legal). On
+ *     any error nothing is launched and nothing changes. cams are the frames
+ *     of the step whose modes are refined, with their T_base_cam (the caller
+ *     passes the right ones); host or device frames, any step_bytes >= 3 W.
+ *  2. Modes. out->modes is mantis_mcl_modes(ctx, max_modes, ...)'s answer from
+ *     the same state, byte for byte, and is cached the same way
+ *     (mantis_mcl_select_mode may follow). After a lost step, or with n_modes =
+ *     0: MANTIS_OK, no refinement is launched, every mode[k] is zero.
+ *  3. Refine. Mode k < n_modes is refined from modes.mode[k].T_w_b on the
+ *     n_cams frames: mode[k].refine is, byte for byte, mantis_refine_batch's
+ *     result for rig k given the same frames repeated once per mode and the
+ *     modes' poses as T_w_b_in. The frames are staged once and shared by all
+ *     modes. p->record = 1 keeps the record (mantis_get_refine_record, rig =
+ *     mode index).
+ *  4. Plan (A = modes.anchor_T_w_b, g = config.grid_spacing, keys and bins as
+ *     in the modes section): key_kept[k] = refine.refined && bin of
+ *     key(T_ref,k, A, g) == bin of (mode k's ix, iy, yaw_quadrant); applied[k] =
+ *     apply && key_kept[k]; the correction X_k = T_ref,k * inverse(T_mode,k), a
+ *     rigid motion in the world frame.
+ *  5. Recentre (only when some mode is applied). For each particle j of the
+ *     current set (the resampled one if the step resampled, as in
+ *     mantis_mcl_select_mode): b = bin of key(T_j, A, g); if an applied mode
+ *     has bin b, T_j <- X_k * T_j (the plain product of the 3 x 3 bases and
+ *     origins, no re-orthonormalisation); otherwise T_j keeps its bits. The
+ *     log-weights, q, the prior pose and the cv::RNG state are untouched.
+ *     n_moved counts the particles moved. The last step's record survives: if
+ *     the current set lies in the buffer of the record's predicted poses (the
+ *     step did not resample) all N particles, moved or copied, go to the other
+ *     buffer, which becomes the current set; otherwise they move in place.
+ *     mantis_mcl_get_record, mantis_mcl_modes, mantis_mcl_modes_color and
+ *     mantis_mcl_get_color_record answer after the call exactly as before it.
+ * A mode's mean is equivariant under X_k (the weights q are untouched and the
+ * mean's terms turn with the poses): the moved cluster's weighted mean is
+ * T_ref,k up to rounding, the rotation block of its covariance (base-frame
+ * rotation vectors) is unchanged and its translation block is turned by X_k.R
+ * (X_k.R Cov_t X_k.R^T). A particle near a cell boundary may change its key by
+ * the move: a later mantis_mcl_select_mode keys the moved set.
+ * mantis_mcl_select_mode itself is unchanged and still commits the prior to the
+ * unrefined mode pose; a caller who wants the refined pose as the prior calls
+ * mantis_set_prior_pose.
+ * Device work, all on the context stream: the modes launch and its copy back,
+ * 2 (I + 1) refinement launches and one copy back of the modes' states, then,
+ * only when a mode is applied, one k_mcl_recentre launch and the copy back of
+ * its 8 counters (the plan needs the refined poses and the host's gate, so it
+ * is formed between the two and travels as kernel arguments). */
+typedef struct mantis_mcl_mode_refined {
+  int32_t applied;   /* 1: this mode's particles of the current set were moved */
+  int32_t key_kept;  /* 1: the refined pose has the mode's key against the anchor */
+  int32_t n_moved;   /* particles of the current set moved with this mode (0 unless applied) */
+  int32_t pad;
+  mantis_refine_result refine; /* of the mode's T_w_b; zeros past n_modes */
+} mantis_mcl_mode_refined;
+/* A tag like struct mantis_mcl_modes, which it holds: write `struct mantis_mcl_refined` in C. */
+struct mantis_mcl_refined {
+  int32_t status, n_modes, apply, n_moved; /* n_moved: over all modes */
+  struct mantis_mcl_modes modes;           /* exactly mantis_mcl_modes's answer */
+  mantis_mcl_mode_refined mode[8];         /* in mode order */
+};
+/* sizeof(mantis_mcl_mode_refined), sizeof(struct mantis_mcl_refined) (host only) */
+void mantis_mcl_refine_sizes(int32_t* mode_bytes, int32_t* refined_bytes);
+mantis_status mantis_mcl_refine_modes(void* ctx, const mantis_image* cams, int32_t n_cams, int32_t max_modes,
+                                      const mantis_refine_params* p, int32_t apply, struct mantis_mcl_refined* out);
+
 #ifdef __cplusplus
 }
 #endif

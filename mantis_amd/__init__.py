@@ -115,6 +115,16 @@ class MantisRefineResult(C.Structure):
                 ("delta", (C.c_double * 6) * 10), ("covariance", C.c_double * 36)]
 
 
+class MantisMclModeRefined(C.Structure):
+    _fields_ = [("applied", C.c_int32), ("key_kept", C.c_int32), ("n_moved", C.c_int32), ("pad", C.c_int32),
+                ("refine", MantisRefineResult)]
+
+
+class MantisMclRefined(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_modes", C.c_int32), ("apply", C.c_int32), ("n_moved", C.c_int32),
+                ("modes", MantisMclModes), ("mode", MantisMclModeRefined * 8)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -246,6 +256,9 @@ _SIGS = {
                                 C.POINTER(MantisRefineParams), C.POINTER(MantisResult),
                                 C.POINTER(MantisRefineResult)]),
     "mantis_get_refine_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "mantis_mcl_refine_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_mcl_refine_modes": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32,
+                                          C.POINTER(MantisRefineParams), C.c_int32, C.POINTER(MantisMclRefined)]),
 }
 
 
@@ -724,6 +737,23 @@ class Mantis:
         e, n = np.zeros(8), np.zeros(8, np.int32)
         self._chk(lib().mantis_mcl_modes_color(self.h, e.ctypes.data, n.ctypes.data), "mcl_modes_color")
         return e, n
+
+    def mcl_refine_modes(self, images, max_modes=8, apply=False, **refine_params):
+        """mantis_mcl_refine_modes: every mode of the last step refined on the
+        grid lines of that step's frames `images`; apply=True also moves each
+        refined mode's particles rigidly onto its refined pose (once per
+        step). Returns the MantisMclRefined record (its `modes` is
+        mcl_modes(max_modes)'s answer); with record=1 refine_record(k, pass)
+        reads mode k's passes."""
+        n = len(images)
+        cams = (MantisImage * n)(*images)
+        p = self.refine_params(**refine_params)
+        out = MantisMclRefined()
+        self._chk(lib().mantis_mcl_refine_modes(self.h, cams, n, max_modes, C.byref(p), 1 if apply else 0,
+                                                C.byref(out)), "mcl_refine_modes")
+        if out.n_modes > 0:
+            self._refine_slots = n * out.mode[0].refine.n_cand
+        return out
 
     def process_sharded(self, images, rigs, cam_index, cams_per_rig):
         """Camera-sharded rig call (mantis_process_rig_sharded): images are this

@@ -317,6 +317,10 @@ struct Ctx {
     bool has_modes = false;  // mantis_mcl_modes has run since the last step
     struct mantis_mcl_modes modes;  // its answer: what mantis_mcl_select_mode commits to
     double modes_g = 0;             // the grid spacing its keys were taken with
+    // the modes refined (mcl_refine_impl.hip): mantis_mcl_refine_modes(apply = 1) has moved particles since
+    // the last step; the 8 per-mode counters of k_mcl_recentre and their pinned copy
+    bool recentred = false;
+    int32_t *d_moved = nullptr, *h_moved = nullptr;
     // the colour evidence (mcl_color_impl.hip): what mantis_mcl_set_color left (enable 0 until then), the
     // (csum, cn) of the last step with colour on, N x C, its pooled Ec and charge, N
     mantis_mcl_color_params color{};
@@ -1379,7 +1383,7 @@ mantis_status mantis_destroy(void* ctx) {
   for (void* p : tptrs)
     if (p) (void)hipFree(p);
   void* mptrs[] = {c->mcl.d_T[0], c->mcl.d_T[1], c->mcl.d_L, c->mcl.d_Lprev, c->mcl.d_q, c->mcl.d_cum, c->mcl.d_anc,
-                   c->mcl.d_in, c->mcl.d_c2w, c->mcl.d_pf, c->mcl.d_sums, c->mcl.d_cnt, c->mcl.d_res, c->mcl.d_modes,
+                   c->mcl.d_in, c->mcl.d_c2w, c->mcl.d_pf, c->mcl.d_sums, c->mcl.d_cnt, c->mcl.d_res, c->mcl.d_modes, c->mcl.d_moved,
                    c->mcl.d_csums, c->mcl.d_ccnt, c->mcl.d_Ec, c->mcl.d_charge};
   for (void* p : mptrs)
     if (p) (void)hipFree(p);
@@ -1389,7 +1393,7 @@ mantis_status mantis_destroy(void* ctx) {
   if (c->rf.h_state) (void)hipHostFree(c->rf.h_state);
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
-                   c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes};
+                   c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes, c->mcl.h_moved};
   for (void* p : hptrs)
     if (p) (void)hipHostFree(p);
   for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -2241,4 +2245,5 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "mcl_modes_impl.hip"
 #include "mcl_color_impl.hip"
 #include "refine_impl.hip"
+#include "mcl_refine_impl.hip"
 #include "ros_wire.h"

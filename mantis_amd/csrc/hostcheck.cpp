@@ -19,6 +19,7 @@ static int g_jacobi_ff = 1;
 #include "mk_mcl.h"
 #include "mk_mcl_color.h"
 #include "mk_mcl_modes.h"
+#include "mk_mcl_refine.h"
 #include "mk_refine.h"
 #include "mk_rpp.h"
 #include "mk_screen.h"
@@ -611,5 +612,33 @@ void hc_refine_conclude(const double* acc28, int min_obs, double max_rms, mantis
 }
 int hc_sizeof_refine_params(void) { return (int)sizeof(mantis_refine_params); }
 int hc_sizeof_refine_result(void) { return (int)sizeof(mantis_refine_result); }
+
+// The modes refined (mk_mcl_refine.h): the rules mantis_mcl_refine_modes and k_mcl_recentre run.
+// modes: a struct mantis_mcl_modes; T_ref 8 x 16 (row-major), refined 8; out: key_kept / applied (8
+// each), X 8 x 16 (the corrections; the identity past n_modes), bins 8 (-1: not applied)
+void hc_mcl_refine_plan(const void* modes, double g, const double* T_ref, const int32_t* refined, int apply,
+                        int32_t* key_kept, int32_t* applied, double* X, int32_t* bins) {
+  mk::mcl::Recentre P;
+  mk::mcl::refine_plan(*(const mk::mcl::Modes*)modes, g, T_ref, refined, apply, key_kept, applied, &P);
+  for (int k = 0; k < mk::mcl::kMaxModes; k++) {
+    mk::track::xf_to_mat4(P.X[k], X + 16 * k);
+    bins[k] = P.bin[k];
+  }
+}
+// the plan of (modes, T_ref, refined, apply) applied to the set T (N x 16 row-major, in / out); n_moved 8
+void hc_mcl_recentre(const void* modes, double g, const double* T_ref, const int32_t* refined, int apply, double* T,
+                     int N, int32_t* n_moved) {
+  mk::mcl::Recentre P;
+  int32_t kept[mk::mcl::kMaxModes], applied[mk::mcl::kMaxModes];
+  mk::mcl::refine_plan(*(const mk::mcl::Modes*)modes, g, T_ref, refined, apply, kept, applied, &P);
+  for (int k = 0; k < mk::mcl::kMaxModes; k++) n_moved[k] = 0;
+  for (int j = 0; j < N; j++) {
+    mk::Xf X = mk::track::xf_from_mat4(T + 16 * (size_t)j);
+    const int32_t hit = mk::mcl::recentre_pose(P, X);
+    if (hit < 0) continue;  // keeps its bits
+    n_moved[hit]++;
+    mk::track::xf_to_mat4(X, T + 16 * (size_t)j);
+  }
+}
 
 }  // extern "C"

@@ -343,6 +343,7 @@ mantis_status mcl_upload(Ctx* c, const std::vector<Xf>& T, const mantis_mcl_para
   m.cur = 0;
   m.has_record = false;
   m.has_modes = false;
+  m.recentred = false;
   m.live = true;
   return MANTIS_OK;
 }
@@ -478,6 +479,7 @@ mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cam
     if (mantis_status e = mcl_color_workspace(c)) return e;
   m.has_record = false;
   m.has_modes = false;  // the modes are the last step's
+  m.recentred = false;  // and so is a correction of them (mantis_mcl_refine_modes)
   int W, H;
   mantis_status st = stage_frames(c, cams, C, W, H);
   if (st != MANTIS_OK) return st;

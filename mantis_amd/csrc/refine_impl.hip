@@ -27,14 +27,15 @@ struct RefineRig {  // one rig between the launches, and what comes back
 };
 
 struct RefineArgs {
-  const GnCam* gncam;   // rigs x C: inverse(T_base_cam)
+  const GnCam* gncam;   // per frame: inverse(T_base_cam)
   const int32_t* cand;  // n_cand: landmark | axis << 16
   RefineRig* st;        // rigs
   rfn::Slot* slots;     // [pass][rig][C n_cand]; pass_slots = the stride between passes (record) or 0
   double* recT;         // [pass][rig][16]: the pose each pass observed at
   double* recAcc;       // [pass][rig][28]
   size_t pass_slots;
-  int32_t C, n_cand, I, n_rigs, min_obs, pad;
+  int32_t C, n_cand, I, n_rigs, min_obs;
+  int32_t rig_stride;   // frame of (rig, cam) = rig * rig_stride + cam: C, or 0 when the rigs share C frames
   rfn::Window win;
   double lambda;
 };
@@ -43,18 +44,20 @@ constexpr int kRefineCands = 32;  // candidates of a k_refine_obs block: 4 trips
 
 // Block (candidate chunk, camera, rig): each wave takes two candidates at a
 // time, one per 32-lane half; lane l <= 2 R of a half is sample k = l - R. The
-// pose and the camera come from the grid, so they are wave-uniform (scalar)
-// loads; the candidate's geometry (a few dozen FP64 operations) is redone by
-// every lane of the half rather than broadcast. One distort and one pixel load
-// per lane, integer sums by __shfl_xor inside the half, one plain store of the
-// slot by lane 0 of the half: every slot has exactly one writer.
+// pose and the camera come from the grid and the kernel arguments (rig_stride:
+// the mode path of mcl_refine_impl.hip reads the same C frames for every rig),
+// so they are wave-uniform (scalar) loads; the candidate's geometry (a few
+// dozen FP64 operations) is redone by every lane of the half rather than
+// broadcast. One distort and one pixel load per lane, integer sums by
+// __shfl_xor inside the half, one plain store of the slot by lane 0 of the
+// half: every slot has exactly one writer.
 __global__ __launch_bounds__(256) void k_refine_obs(const FrameDesc* __restrict__ frames, Landmarks lmk, RefineArgs a,
                                                     int pass) {
   const int chunk = blockIdx.x, cam = blockIdx.y, rig = blockIdx.z;
   const RefineRig& S = a.st[rig];
   if (S.done) return;  // block-uniform: the rig stopped in an earlier pass
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, half = lane >> 5, l = lane & 31;
-  const int f = rig * a.C + cam;
+  const int f = rig * a.rig_stride + cam;
   const Cam cm = frames[f].cam;
   const uint8_t* bgr = frames[f].bgr;
   const int W = frames[f].w, H = frames[f].h, npx = W * H;
@@ -64,7 +67,7 @@ __global__ __launch_bounds__(256) void k_refine_obs(const FrameDesc* __restrict_
   const double s = 1.0 / cm.fx;
   const int R = a.win.R, k = l - R;
   const bool active = l <= 2 * R;
-  rfn::Slot* out = a.slots + (size_t)pass * a.pass_slots + (size_t)f * a.n_cand;
+  rfn::Slot* out = a.slots + (size_t)pass * a.pass_slots + (size_t)(rig * a.C + cam) * a.n_cand;
   const int c0 = chunk * kRefineCands, c1 = min(c0 + kRefineCands, a.n_cand);
   for (int base = c0 + wave * 2; base < c1; base += 8) {  // wave-uniform trips: every lane reaches the shuffles
     const int ci = base + half;
@@ -191,13 +194,13 @@ mantis_status refine_flags(Ctx* c, double pitch) {
   return MANTIS_OK;
 }
 
-// workspaces for a call of R rigs x C cameras, I iterations
-mantis_status refine_workspace(Ctx* c, int R, int C, int I, bool record) {
+// workspaces for a call of R rigs x C cameras on F frames, I iterations
+mantis_status refine_workspace(Ctx* c, int R, int C, int F, int I, bool record) {
   Ctx::Refine& r = c->rf;
   const size_t slots = (record ? (size_t)I + 1 : 1) * R * C * std::max(r.n_cand, 1);
-  if (R > r.rig_cap || R * C > r.cam_cap || slots > r.slot_cap) HIP_OK(hipStreamSynchronize(c->s));
-  if (R > r.rig_cap || R * C > r.cam_cap) {
-    const int rc = std::max(R, r.rig_cap), cc = std::max(R * C, r.cam_cap);
+  if (R > r.rig_cap || F > r.cam_cap || slots > r.slot_cap) HIP_OK(hipStreamSynchronize(c->s));
+  if (R > r.rig_cap || F > r.cam_cap) {
+    const int rc = std::max(R, r.rig_cap), cc = std::max(F, r.cam_cap);
     r.rig_cap = r.cam_cap = 0;
     if (r.h_state) (void)hipHostFree(r.h_state);
     r.h_state = nullptr;
@@ -218,9 +221,8 @@ mantis_status refine_workspace(Ctx* c, int R, int C, int I, bool record) {
   return MANTIS_OK;
 }
 
-mantis_status refine_impl(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32_t C, const double* T_in,
-                          const mantis_refine_params* p, mantis_refine_result* out) {
-  if (!cams || !T_in || !p || !out) return refine_fail(c, "null argument");
+// the parameter and frame checks of a call of n_rigs x C frames (cams, p: not null)
+mantis_status refine_check(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32_t C, const mantis_refine_params* p) {
   if (p->struct_size != (int32_t)sizeof(mantis_refine_params)) return refine_fail(c, "params.struct_size mismatch");
   if (!c->d_lm || c->nw + c->nr + c->ng <= 0) return refine_fail(c, "map not set (mantis_set_map)");
   if (n_rigs <= 0 || C <= 0) return refine_fail(c, "n_rigs and cams_per_rig must be positive");
@@ -246,13 +248,20 @@ mantis_status refine_impl(Ctx* c, const mantis_image* cams, int32_t n_rigs, int3
   }
   if (cams[0].width <= 2 || cams[0].height <= 2 || cams[0].width > c->Wmax || cams[0].height > c->Hmax)
     return refine_fail(c, "image size outside [3, max]");
-  for (int i = 0; i < 16 * n_rigs; i++)
-    if (!std::isfinite(T_in[i])) return refine_fail(c, "T_w_b_in is not finite");
+  return MANTIS_OK;
+}
 
+// The device work of a checked call: n_rigs rigs of C cameras from T_in. Rig r
+// reads frames r * C .. r * C + C - 1 of n_rigs x C (shared = false), or every
+// rig the same C frames, staged once (shared = true: the modes of
+// mantis_mcl_refine_modes).
+mantis_status refine_run(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32_t C, bool shared, const double* T_in,
+                         const mantis_refine_params* p, mantis_refine_result* out) {
+  const int I = p->iterations, n = shared ? C : n_rigs * C;
   Ctx::Refine& r = c->rf;
   r.rigs = 0;  // no record until this call has finished
   if (mantis_status e = refine_flags(c, p->landmark_pitch)) return e;
-  if (mantis_status e = refine_workspace(c, n_rigs, C, I, p->record != 0)) return e;
+  if (mantis_status e = refine_workspace(c, n_rigs, C, n, I, p->record != 0)) return e;
 
   mk::RefineRig* h_st = (mk::RefineRig*)r.h_state;
   mk::GnCam* h_gc = (mk::GnCam*)(h_st + r.rig_cap);
@@ -276,13 +285,13 @@ mantis_status refine_impl(Ctx* c, const mantis_image* cams, int32_t n_rigs, int3
   a.slots = (rfn::Slot*)r.d_slots;
   a.recT = r.d_recT;
   a.recAcc = r.d_recAcc;
-  a.pass_slots = p->record ? (size_t)n * r.n_cand : 0;
+  a.pass_slots = p->record ? (size_t)n_rigs * C * r.n_cand : 0;
   a.C = C;
   a.n_cand = r.n_cand;
   a.I = I;
   a.n_rigs = n_rigs;
   a.min_obs = p->min_obs;
-  a.pad = 0;
+  a.rig_stride = shared ? 0 : C;
   a.win = rfn::Window{p->half_window, p->white_thresh, p->min_weight, 0};
   a.lambda = p->lambda;
   const Landmarks L = lmk_of(c);
@@ -313,6 +322,15 @@ mantis_status refine_impl(Ctx* c, const mantis_image* cams, int32_t n_rigs, int3
   r.record = p->record;
   r.cands = r.n_cand;
   return MANTIS_OK;
+}
+
+mantis_status refine_impl(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32_t C, const double* T_in,
+                          const mantis_refine_params* p, mantis_refine_result* out) {
+  if (!cams || !T_in || !p || !out) return refine_fail(c, "null argument");
+  if (mantis_status e = refine_check(c, cams, n_rigs, C, p)) return e;
+  for (int i = 0; i < 16 * n_rigs; i++)
+    if (!std::isfinite(T_in[i])) return refine_fail(c, "T_w_b_in is not finite");
+  return refine_run(c, cams, n_rigs, C, false, T_in, p, out);
 }
 
 }  // namespace
