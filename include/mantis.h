@@ -810,6 +810,81 @@ mantis_status mantis_refine(void* ctx, const mantis_image* cams, int32_t n_cams,
 mantis_status mantis_get_refine_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, int32_t* codes,
                                        int32_t* Sw, int32_t* Skw, double* rows, double* acc28);
 
+/* ---- Line refinement, robust rows: Huber / Tukey weights from a median ----
+ * The refinement above gives every code-0 row the same weight. With this
+ * switch on, each pass reweights its rows by how far their offset lies from
+ * the pass's median offset (iteratively reweighted least squares), so that
+ * rows which found the wrong thing -- a camera whose extrinsic has drifted, a
+ * line of another colour inside the window -- pull less (Huber) or not at all
+ * (Tukey). Off by default and switched per context; all addition:
+ * mantis_refine_params and mantis_refine_result keep their sizes,
+ * MANTIS_ABI_VERSION stays 5 (find the entries by name, check the sizes with
+ * mantis_refine_robust_sizes), and with the switch off every refine entry
+ * point returns the bytes it returned before.
+ *
+ * At every pass k = 0 .. I (the final pass included), after the observations
+ * and before the accumulation, over the rig's C n_cand slots:
+ *  1. key of a code-0 slot = floor(|Skw| 2^20 / Sw) in 64-bit integers: the
+ *     row's offset in sample steps (about pixels, whatever fx) in units of
+ *     2^-20. Sw <= 31 x 195075 < 2^23 and |Skw| <= 15 Sw, so key < 2^24
+ *     (uint32). Rejected slots have key 0 and weight 0 in the record.
+ *  2. n = the code-0 count, m = the key of rank floor((n - 1) / 2) in
+ *     ascending order (the lower median); n = 0: m = 0. An integer: the same
+ *     bits by any selection method.
+ *  3. scale sigma = max(1.4826 ((double)m / 2^20), scale_floor), in steps.
+ *  4. u = (double)key / 2^20, t = u / (tuning sigma).
+ *     Huber: w = 1 if t <= 1, else 1 / t.
+ *     Tukey: w = (1 - t t)^2 if t < 1, else 0.
+ *  5. the accumulated row is sqrt(w) [J | r]: acc28 = J^T W J, J^T W r, r^T W r.
+ *  6. the end of the pass as above on the weighted acc28 (rms = sqrt(r^T W r /
+ *     n_obs), n_obs still the code-0 count), and STARVED also when fewer than
+ *     min_obs rows have w > 0.
+ *  7. the gate and the covariance as above: (r^T W r / (n_obs - 6)) (J^T W J)^-1.
+ *  8. mantis_get_refine_record keeps returning the unweighted rows (its acc28
+ *     is the weighted one the pass solved); keys and weights are read with
+ *     mantis_get_refine_robust_record.
+ * mantis_refine, mantis_refine_batch and mantis_mcl_refine_modes all take the
+ * context's setting, and mantis_mcl_refine_modes' mode[k].refine stays, byte
+ * for byte, mantis_refine_batch's result for the same frames and poses with
+ * the switch on as with it off. Device work: k_refine_step_robust in place of
+ * k_refine_step, still 2 (I + 1) launches, and one more copy back (the stats). */
+typedef struct mantis_refine_robust_params {
+  int32_t struct_size;  /* sizeof(mantis_refine_robust_params) */
+  int32_t loss;         /* 0 none, 1 Huber, 2 Tukey */
+  double tuning;        /* finite, > 0 */
+  double scale_floor;   /* finite, > 0, in sample steps */
+} mantis_refine_robust_params;
+/* loss as given; tuning 1.345 (4.685 for loss = 2); scale_floor 0.25 */
+void mantis_default_refine_robust_params(int32_t loss, mantis_refine_robust_params* p);
+
+typedef struct mantis_refine_robust_stats {
+  int32_t loss, pad;
+  uint32_t median_key[11]; /* per pass; entries past iterations_run are 0 */
+  int32_t n_down[11];      /* rows with w < 1 */
+  int32_t n_zero[11];      /* rows with w == 0 */
+  double scale[11];        /* sigma */
+  double sum_w[11];        /* sum of w over the code-0 rows */
+} mantis_refine_robust_stats;
+/* sizeof(mantis_refine_robust_params), sizeof(mantis_refine_robust_stats) (host only) */
+void mantis_refine_robust_sizes(int32_t* params_bytes, int32_t* stats_bytes);
+
+/* The context's setting: NULL or loss = 0 switches the robust rows off (the
+ * other fields are then not read). May be called any time after
+ * mantis_create, is kept across calls and applies from the next refine call.
+ * Host only. MANTIS_ERR_ARG (the setting stays; mantis_last_error names the
+ * field): struct_size, loss outside 0..2, tuning or scale_floor not finite
+ * and > 0. */
+mantis_status mantis_refine_set_robust(void* ctx, const mantis_refine_robust_params* p);
+/* The stats of rig `rig` of the last refine call. MANTIS_ERR_STATE: no refine
+ * call yet, or the last one ran with the switch off. MANTIS_ERR_ARG: null,
+ * rig out of range. */
+mantis_status mantis_get_refine_robust(void* ctx, int32_t rig, mantis_refine_robust_stats* stats);
+/* Keys and weights (each nullable) of rig `rig`, pass 0 .. iterations_run, of
+ * the last refine call, which must have run with the switch on and record =
+ * 1 (else MANTIS_ERR_STATE): one entry per slot (C x n_cand), 0 in rejected
+ * slots. MANTIS_ERR_ARG: rig or pass out of range. */
+mantis_status mantis_get_refine_robust_record(void* ctx, int32_t rig, int32_t pass, uint32_t* keys, double* weights);
+
 /* ---- Monte Carlo localization: the modes refined on the grid lines ----
  * A mode of mantis_mcl_modes is a weighted mean over a cell: its resolution is
  * the particle spacing and its covariance the set's scatter. This call refines

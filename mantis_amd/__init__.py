@@ -115,6 +115,15 @@ class MantisRefineResult(C.Structure):
                 ("delta", (C.c_double * 6) * 10), ("covariance", C.c_double * 36)]
 
 
+class MantisRefineRobustParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("loss", C.c_int32), ("tuning", C.c_double), ("scale_floor", C.c_double)]
+
+
+class MantisRefineRobustStats(C.Structure):
+    _fields_ = [("loss", C.c_int32), ("pad", C.c_int32), ("median_key", C.c_uint32 * 11), ("n_down", C.c_int32 * 11),
+                ("n_zero", C.c_int32 * 11), ("scale", C.c_double * 11), ("sum_w", C.c_double * 11)]
+
+
 class MantisMclModeRefined(C.Structure):
     _fields_ = [("applied", C.c_int32), ("key_kept", C.c_int32), ("n_moved", C.c_int32), ("pad", C.c_int32),
                 ("refine", MantisRefineResult)]
@@ -256,6 +265,11 @@ _SIGS = {
                                 C.POINTER(MantisRefineParams), C.POINTER(MantisResult),
                                 C.POINTER(MantisRefineResult)]),
     "mantis_get_refine_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "mantis_default_refine_robust_params": (None, [C.c_int32, C.POINTER(MantisRefineRobustParams)]),
+    "mantis_refine_robust_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_refine_set_robust": (C.c_int, [C.c_void_p, C.POINTER(MantisRefineRobustParams)]),
+    "mantis_get_refine_robust": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MantisRefineRobustStats)]),
+    "mantis_get_refine_robust_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mantis_mcl_refine_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mantis_mcl_refine_modes": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32,
                                           C.POINTER(MantisRefineParams), C.c_int32, C.POINTER(MantisMclRefined)]),
@@ -606,6 +620,44 @@ class Mantis:
                                                  Skw.ctypes.data, rows.ctypes.data, acc.ctypes.data),
                   "get_refine_record")
         return T, codes, Sw, Skw, rows, acc
+
+    REFINE_LOSSES = {None: 0, "none": 0, "huber": 1, "tukey": 2}
+
+    def set_refine_robust(self, loss=None, **params):
+        """mantis_refine_set_robust: the robust rows of every later refine call
+        on this context (refine, refine_batch, mcl_refine_modes). loss: None
+        (NULL: off), 0 / "none", 1 / "huber", 2 / "tukey"; `tuning` and
+        `scale_floor` override mantis_default_refine_robust_params."""
+        if loss is None and not params:
+            self._chk(lib().mantis_refine_set_robust(self.h, None), "refine_set_robust")
+            return
+        p = MantisRefineRobustParams()
+        lib().mantis_default_refine_robust_params(self.REFINE_LOSSES.get(loss, loss), C.byref(p))
+        for k, v in params.items():
+            if k not in ("tuning", "scale_floor"):
+                raise TypeError(f"refine robust: unknown parameter {k!r}")
+            setattr(p, k, v)
+        self._chk(lib().mantis_refine_set_robust(self.h, C.byref(p)), "refine_set_robust")
+
+    def refine_robust_stats(self, rig=0):
+        """mantis_get_refine_robust: the MantisRefineRobustStats of rig `rig` of
+        the last refine call (made with the robust rows on)."""
+        st = MantisRefineRobustStats()
+        self._chk(lib().mantis_get_refine_robust(self.h, rig, C.byref(st)), "get_refine_robust")
+        return st
+
+    def refine_robust_record(self, rig, pass_):
+        """mantis_get_refine_robust_record: (keys uint32 [slots], weights
+        [slots]) of pass `pass_` of rig `rig` of the last refine call, made
+        with the robust rows on and record=1; 0 in rejected slots."""
+        ns = getattr(self, "_refine_slots", None)
+        if ns is None:
+            raise MantisError("refine_robust_record: no refine call on this context")
+        keys = np.zeros(ns, np.uint32)
+        w = np.zeros(ns)
+        self._chk(lib().mantis_get_refine_robust_record(self.h, rig, pass_, keys.ctypes.data, w.ctypes.data),
+                  "get_refine_robust_record")
+        return keys, w
 
     def line_flags(self, pitch=0.08):
         """mantis_refine_line_flags: one byte per landmark of the current map

@@ -347,6 +347,16 @@ struct Ctx {
     size_t slot_cap = 0;
     int rigs = 0, C = 0, I = 0, record = 0, cands = 0;  // the last call
     std::vector<int32_t> runs;                          // its rigs' iterations_run
+    // the robust rows (refine_robust_impl.hip): what mantis_refine_set_robust left (loss 0 until
+    // then), the rigs' stats (d: per call, h: pinned, of the last call) and, for a record, every
+    // pass's keys and weights laid out as d_slots
+    mantis_refine_robust_params robust{};
+    mantis_refine_robust_stats *d_rstats = nullptr, *h_rstats = nullptr;
+    int rstat_cap = 0;
+    uint32_t* d_rkeys = nullptr;
+    double* d_rweights = nullptr;
+    size_t rslot_cap = 0;
+    int rec_loss = 0;  // the last call's loss
   } rf;
 };
 
@@ -1387,10 +1397,12 @@ mantis_status mantis_destroy(void* ctx) {
                    c->mcl.d_csums, c->mcl.d_ccnt, c->mcl.d_Ec, c->mcl.d_charge};
   for (void* p : mptrs)
     if (p) (void)hipFree(p);
-  void* rptrs[] = {c->rf.d_cand, c->rf.d_gncam, c->rf.d_state, c->rf.d_recT, c->rf.d_recAcc, c->rf.d_slots};
+  void* rptrs[] = {c->rf.d_cand, c->rf.d_gncam, c->rf.d_state, c->rf.d_recT, c->rf.d_recAcc, c->rf.d_slots,
+                   c->rf.d_rstats, c->rf.d_rkeys, c->rf.d_rweights};
   for (void* p : rptrs)
     if (p) (void)hipFree(p);
   if (c->rf.h_state) (void)hipHostFree(c->rf.h_state);
+  if (c->rf.h_rstats) (void)hipHostFree(c->rf.h_rstats);
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
                    c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes, c->mcl.h_moved};

@@ -613,6 +613,51 @@ void hc_refine_conclude(const double* acc28, int min_obs, double max_rms, mantis
 int hc_sizeof_refine_params(void) { return (int)sizeof(mantis_refine_params); }
 int hc_sizeof_refine_result(void) { return (int)sizeof(mantis_refine_result); }
 
+// The robust rows (mk_refine.h robust_*): the rules k_refine_step_robust runs.
+uint32_t hc_refine_robust_key(int32_t Sw, int32_t Skw) { return mk::refine::robust_key(Sw, Skw); }
+// keys (n; codes nullable = every slot is a row) to the lower median, the scale, the weights (n, 0
+// in rejected slots) and counts (4: n_obs, n_down, n_zero, n with w > 0); sum_w in slot order
+void hc_refine_robust_weights(const uint32_t* keys, const int32_t* codes, int n, int loss, double tuning,
+                              double scale_floor, double* weights, uint32_t* median_key, double* scale, int32_t* counts,
+                              double* sum_w) {
+  mk::refine::RobustPass P;
+  mk::refine::robust_weights(keys, codes, n, mk::refine::Robust{loss, 0, tuning, scale_floor}, weights, P);
+  *median_key = P.median_key;
+  *scale = P.scale;
+  counts[0] = P.n_obs;
+  counts[1] = P.n_down;
+  counts[2] = P.n_zero;
+  counts[3] = P.n_obs - P.n_zero;
+  *sum_w = P.sum_w;
+}
+// hc_refine_seq with the robust rows of rb (null or loss 0: hc_refine_seq's bytes); stats nullable
+void hc_refine_seq_robust(const double* T_in, const double* Tbc, const double* K, const double* D,
+                          const uint8_t* const* frames, int C, int W, int H, const double* X, int nw, int nr, int ng,
+                          const mantis_refine_params* p, const mantis_refine_robust_params* rb,
+                          mantis_refine_result* out, mantis_refine_robust_stats* stats) {
+  namespace rf = mk::refine;
+  const int n = nw + nr + ng;
+  std::vector<uint8_t> flags(n > 0 ? n : 1);
+  rf::line_flags(X, n, p->landmark_pitch, flags.data());
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags.data(), n, cand.data());
+  std::vector<mk::GnCam> gc(C);
+  std::vector<mk::Cam> cm(C);
+  for (int c = 0; c < C; c++) {
+    rf::gncam_from(Tbc + 16 * c, gc[c]);
+    cm[c] = hc_cam(K + 9 * c, D + 4 * c);
+  }
+  const rf::Robust r = rb ? rf::Robust{rb->loss, 0, rb->tuning, rb->scale_floor} : rf::Robust{0, 0, 1.0, 1.0};
+  rf::refine_seq_robust(T_in, gc.data(), cm.data(), frames, C, W, H, X, nw, nr, cand.data(), nc, *p, r, *out, stats);
+}
+// one step of a pass with the starved gate of the robust rows: returns 1 when the rig is finished
+int hc_refine_end_pass_robust(const double* acc28, int n_obs, int n_pos, int pass, int I, int min_obs, double lambda,
+                              mantis_refine_result* R) {
+  return mk::refine::end_pass_robust(acc28, n_obs, n_pos, pass, I, min_obs, lambda, *R) ? 1 : 0;
+}
+int hc_sizeof_refine_robust_params(void) { return (int)sizeof(mantis_refine_robust_params); }
+int hc_sizeof_refine_robust_stats(void) { return (int)sizeof(mantis_refine_robust_stats); }
+
 // The modes refined (mk_mcl_refine.h): the rules mantis_mcl_refine_modes and k_mcl_recentre run.
 // modes: a struct mantis_mcl_modes; T_ref 8 x 16 (row-major), refined 8; out: key_kept / applied (8
 // each), X 8 x 16 (the corrections; the identity past n_modes), bins 8 (-1: not applied)

@@ -5,12 +5,15 @@
 // samples that look like the landmark's set colour is where the line really
 // is, and its signed offset is a point-to-line residual for the right-
 // perturbation rows of mk_gn.h. The rules here are shared by the device
-// (k_refine_obs / k_refine_step, refine_impl.hip) and the host build of the
-// CPU tests (hostcheck.cpp hc_refine_*, tools/refinecheck_main.cpp). Both
-// builds keep -ffp-contract=off.
+// (k_refine_obs / k_refine_step, refine_impl.hip; k_refine_step_robust,
+// refine_robust_impl.hip) and the host build of the CPU tests (hostcheck.cpp
+// hc_refine_*, tools/refinecheck_main.cpp). Both builds keep
+// -ffp-contract=off.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "mk_gn.h"
 
@@ -233,6 +236,82 @@ MK_HD bool end_pass(const double* acc28, int32_t n_obs, int pass, int I, int32_t
   return false;
 }
 
+// ---- robust rows (mantis_refine_set_robust, include/mantis.h): the weight of
+// a code-0 row from its integer key and the pass's median key. Shared by
+// k_refine_step_robust (refine_robust_impl.hip) and the host (robust_pass).
+constexpr int kLossNone = 0, kLossHuber = 1, kLossTukey = 2;
+constexpr double kKeyUnit = 1048576.0;  // 2^20 keys per sample step
+
+struct Robust {  // what a pass needs of mantis_refine_robust_params
+  int32_t loss, pad;
+  double tuning, scale_floor;
+};
+
+// floor(|Skw| 2^20 / Sw) of a code-0 slot (Sw >= 1, |Skw| <= 15 Sw: below 2^24)
+MK_HD uint32_t robust_key(int32_t Sw, int32_t Skw) {
+  const int64_t a = Skw < 0 ? -(int64_t)Skw : (int64_t)Skw;
+  return (uint32_t)((a << 20) / (int64_t)Sw);
+}
+MK_HD double robust_scale(uint32_t median_key, double scale_floor) {
+  const double s = 1.4826 * ((double)median_key / kKeyUnit);
+  return s > scale_floor ? s : scale_floor;
+}
+MK_HD double robust_weight(uint32_t key, const Robust& rb, double sigma) {
+  const double u = (double)key / kKeyUnit, t = u / (rb.tuning * sigma);
+  if (rb.loss == kLossHuber) return t <= 1.0 ? 1.0 : 1.0 / t;
+  if (rb.loss == kLossTukey) {
+    const double a = 1.0 - t * t;
+    return t < 1.0 ? a * a : 0.0;
+  }
+  return 1.0;
+}
+// end_pass on the weighted accumulators; n_pos = the rows with w > 0: too few of them starve the pass too
+MK_HD bool end_pass_robust(const double* acc28, int32_t n_obs, int32_t n_pos, int pass, int I, int32_t min_obs,
+                           double lambda, mantis_refine_result& R) {
+  if (pass < I && n_obs >= min_obs && n_pos < min_obs) {
+    R.n_obs[pass] = n_obs;
+    R.rms[pass] = sqrt(acc28[27] / (double)n_obs);  // n_obs >= min_obs > 0
+    R.status = kStarved;
+    return true;
+  }
+  return end_pass(acc28, n_obs, pass, I, min_obs, lambda, R);
+}
+
+// Host: the robust rule over one pass's slots. keys / weights (n each): 0 in
+// rejected slots; the counts and sum_w (in slot order) of the code-0 slots.
+struct RobustPass {
+  uint32_t median_key;
+  int32_t n_obs, n_down, n_zero;
+  double scale, sum_w;
+};
+inline uint32_t robust_median(std::vector<uint32_t>& live) {  // reorders `live`
+  if (live.empty()) return 0;
+  const size_t k = (live.size() - 1) / 2;
+  std::nth_element(live.begin(), live.begin() + k, live.end());
+  return live[k];
+}
+inline void robust_weights(const uint32_t* keys, const int32_t* codes, int n, const Robust& rb, double* weights,
+                           RobustPass& P) {
+  std::vector<uint32_t> live;
+  for (int k = 0; k < n; k++)
+    if (!codes || codes[k] == 0) live.push_back(keys[k]);
+  P = RobustPass{};
+  P.n_obs = (int32_t)live.size();
+  P.median_key = robust_median(live);
+  P.scale = robust_scale(P.median_key, rb.scale_floor);
+  for (int k = 0; k < n; k++) {
+    if (codes && codes[k] != 0) {
+      weights[k] = 0.0;
+      continue;
+    }
+    const double w = robust_weight(keys[k], rb, P.scale);
+    weights[k] = w;
+    P.n_down += w < 1.0;
+    P.n_zero += w == 0.0;
+    P.sum_w += w;
+  }
+}
+
 // Host: the gate and the covariance from the last pass's accumulators.
 // Cov_delta = sigma^2 (J^T J)^-1 by Cholesky, sigma^2 = r^T r / (n_obs - 6),
 // its translation block turned from the base frame to the world frame
@@ -329,6 +408,61 @@ inline void refine_seq(const double* T_in, const GnCam* gcams, const Cam* cams, 
         n_obs += o.code == 0;
       }
     if (end_pass(acc, n_obs, pass, p.iterations, p.min_obs, p.lambda, R)) break;
+  }
+  conclude(acc, p.min_obs, p.max_rms, R);
+}
+
+// refine_seq with the robust rows of `rb` (loss 0: refine_seq's bytes). stats
+// (nullable): the passes' figures. Per pass: all the slots, then their keys,
+// the median and the weights, then sqrt(w) [J | r] summed in slot order.
+inline void refine_seq_robust(const double* T_in, const GnCam* gcams, const Cam* cams, const uint8_t* const* frames,
+                              int C, int W, int H, const double* X, int nw, int nr, const int32_t* cand, int n_cand,
+                              const mantis_refine_params& p, const Robust& rb, mantis_refine_result& R,
+                              mantis_refine_robust_stats* stats) {
+  R = mantis_refine_result{};
+  R.n_cand = n_cand;
+  for (int e = 0; e < 16; e++) R.T_w_b[e] = T_in[e];
+  if (stats) {
+    *stats = mantis_refine_robust_stats{};
+    stats->loss = rb.loss;
+  }
+  const Window win{p.half_window, p.white_thresh, p.min_weight, 0};
+  const int n = C * n_cand;
+  std::vector<Slot> slots(n > 0 ? n : 1);
+  std::vector<uint32_t> keys(n > 0 ? n : 1);
+  std::vector<int32_t> codes(n > 0 ? n : 1);
+  std::vector<double> w(n > 0 ? n : 1);
+  double acc[28];
+  for (int pass = 0; pass <= p.iterations; pass++) {
+    double Rt[9], t[3];
+    pose_parts(R.T_w_b, Rt, t);
+    for (int c = 0; c < C; c++)
+      for (int k = 0; k < n_cand; k++) {
+        const int i = cand[k] & 0xffff, axis = cand[k] >> 16;
+        int tg[3];
+        target_bgr(i, nw, nr, tg);
+        Slot& o = slots[(size_t)c * n_cand + k];
+        observe(Rt, t, gcams[c], cams[c], frames[c], W, H, X + 3 * i, axis, tg, win, o, nullptr);
+        codes[(size_t)c * n_cand + k] = o.code;
+        keys[(size_t)c * n_cand + k] = o.code == 0 ? robust_key(o.Sw, o.Skw) : 0;
+      }
+    RobustPass P;
+    robust_weights(keys.data(), codes.data(), n, rb, w.data(), P);
+    for (int e = 0; e < 28; e++) acc[e] = 0.0;
+    for (int k = 0; k < n; k++) {
+      const double sw = sqrt(w[k]);
+      double v[7];
+      for (int e = 0; e < 7; e++) v[e] = slots[k].row[e] * sw;
+      accumulate_row(v, acc);
+    }
+    if (stats) {
+      stats->median_key[pass] = P.median_key;
+      stats->n_down[pass] = P.n_down;
+      stats->n_zero[pass] = P.n_zero;
+      stats->scale[pass] = P.scale;
+      stats->sum_w[pass] = P.sum_w;
+    }
+    if (end_pass_robust(acc, P.n_obs, P.n_obs - P.n_zero, pass, p.iterations, p.min_obs, p.lambda, R)) break;
   }
   conclude(acc, p.min_obs, p.max_rms, R);
 }

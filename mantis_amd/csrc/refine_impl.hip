@@ -8,7 +8,10 @@
 //   per pass k = 0 .. I:  k_refine_obs   the (camera, candidate) slots at T_k
 //                         k_refine_step  M^T M over the rig's slots, the gates,
 //                                        the solve, T_k+1 (pass I: no solve)
-// = 2 (I + 1) launches, then one D2H copy of the rigs' states. Every hand-off
+//                         (k_refine_step_robust, refine_robust_impl.hip, in its
+//                         place when mantis_refine_set_robust switched it on)
+// = 2 (I + 1) launches, then one D2H copy of the rigs' states (and one of the
+// robust stats). Every hand-off
 // between blocks -- the slots the observation blocks write for the rig's step
 // block, the pose that block writes for the next observation blocks -- crosses
 // a kernel boundary: no last-block counter, no flag polled inside a kernel, no
@@ -157,6 +160,8 @@ __global__ __launch_bounds__(256) void k_refine_step(RefineArgs a, int pass) {
 
 }  // namespace mk
 
+#include "refine_robust_impl.hip"
+
 namespace {
 
 namespace rfn = mk::refine;
@@ -194,11 +199,13 @@ mantis_status refine_flags(Ctx* c, double pitch) {
   return MANTIS_OK;
 }
 
-// workspaces for a call of R rigs x C cameras on F frames, I iterations
-mantis_status refine_workspace(Ctx* c, int R, int C, int F, int I, bool record) {
+// workspaces for a call of R rigs x C cameras on F frames, I iterations; robust: the switch is on
+mantis_status refine_workspace(Ctx* c, int R, int C, int F, int I, bool record, bool robust) {
   Ctx::Refine& r = c->rf;
   const size_t slots = (record ? (size_t)I + 1 : 1) * R * C * std::max(r.n_cand, 1);
-  if (R > r.rig_cap || F > r.cam_cap || slots > r.slot_cap) HIP_OK(hipStreamSynchronize(c->s));
+  const size_t rslots = robust && record ? slots : 0;  // keys and weights: only as a record
+  if (R > r.rig_cap || F > r.cam_cap || slots > r.slot_cap || rslots > r.rslot_cap || (robust && R > r.rstat_cap))
+    HIP_OK(hipStreamSynchronize(c->s));
   if (R > r.rig_cap || F > r.cam_cap) {
     const int rc = std::max(R, r.rig_cap), cc = std::max(F, r.cam_cap);
     r.rig_cap = r.cam_cap = 0;
@@ -217,6 +224,20 @@ mantis_status refine_workspace(Ctx* c, int R, int C, int F, int I, bool record) 
     r.slot_cap = 0;
     if (refine_grow(c, (rfn::Slot**)&r.d_slots, slots)) return MANTIS_ERR_OOM;
     r.slot_cap = slots;
+  }
+  if (robust && R > r.rstat_cap) {
+    r.rstat_cap = 0;
+    if (r.h_rstats) (void)hipHostFree(r.h_rstats);
+    r.h_rstats = nullptr;
+    if (refine_grow(c, &r.d_rstats, (size_t)R) ||
+        halloc(c, (uint8_t**)&r.h_rstats, sizeof(mantis_refine_robust_stats) * R))
+      return MANTIS_ERR_OOM;
+    r.rstat_cap = R;
+  }
+  if (rslots > r.rslot_cap) {
+    r.rslot_cap = 0;
+    if (refine_grow(c, &r.d_rkeys, rslots) || refine_grow(c, &r.d_rweights, rslots)) return MANTIS_ERR_OOM;
+    r.rslot_cap = rslots;
   }
   return MANTIS_OK;
 }
@@ -260,8 +281,9 @@ mantis_status refine_run(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32
   const int I = p->iterations, n = shared ? C : n_rigs * C;
   Ctx::Refine& r = c->rf;
   r.rigs = 0;  // no record until this call has finished
+  const bool robust = r.robust.loss != rfn::kLossNone;  // as mantis_refine_set_robust left it
   if (mantis_status e = refine_flags(c, p->landmark_pitch)) return e;
-  if (mantis_status e = refine_workspace(c, n_rigs, C, n, I, p->record != 0)) return e;
+  if (mantis_status e = refine_workspace(c, n_rigs, C, n, I, p->record != 0, robust)) return e;
 
   mk::RefineRig* h_st = (mk::RefineRig*)r.h_state;
   mk::GnCam* h_gc = (mk::GnCam*)(h_st + r.rig_cap);
@@ -294,6 +316,14 @@ mantis_status refine_run(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32
   a.rig_stride = shared ? 0 : C;
   a.win = rfn::Window{p->half_window, p->white_thresh, p->min_weight, 0};
   a.lambda = p->lambda;
+  mk::RobustArgs rb{};
+  if (robust) {
+    rb.stats = r.d_rstats;
+    rb.keys = p->record ? r.d_rkeys : nullptr;
+    rb.weights = p->record ? r.d_rweights : nullptr;
+    rb.rb = rfn::Robust{r.robust.loss, 0, r.robust.tuning, r.robust.scale_floor};
+    HIP_OK(hipMemsetAsync(r.d_rstats, 0, sizeof(mantis_refine_robust_stats) * n_rigs, c->s));
+  }
   const Landmarks L = lmk_of(c);
   mark(c, "start");
   const dim3 grid((r.n_cand + mk::kRefineCands - 1) / mk::kRefineCands, C, n_rigs);
@@ -303,11 +333,20 @@ mantis_status refine_run(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32
       HIP_OK(hipGetLastError());
     }
     mark(c, "refine_obs/k_refine_obs");
-    mk::k_refine_step<<<n_rigs, 256, 0, c->s>>>(a, pass);
-    HIP_OK(hipGetLastError());
-    mark(c, "refine_step/k_refine_step");
+    if (robust) {
+      mk::k_refine_step_robust<<<n_rigs, 256, 0, c->s>>>(a, rb, pass);
+      HIP_OK(hipGetLastError());
+      mark(c, "refine_step/k_refine_step_robust");
+    } else {
+      mk::k_refine_step<<<n_rigs, 256, 0, c->s>>>(a, pass);
+      HIP_OK(hipGetLastError());
+      mark(c, "refine_step/k_refine_step");
+    }
   }
   HIP_OK(hipMemcpyAsync(h_st, r.d_state, sizeof(mk::RefineRig) * n_rigs, hipMemcpyDeviceToHost, c->s));
+  if (robust)
+    HIP_OK(hipMemcpyAsync(r.h_rstats, r.d_rstats, sizeof(mantis_refine_robust_stats) * n_rigs, hipMemcpyDeviceToHost,
+                          c->s));
   HIP_OK(wait_stream(c, n));
   finish_profile(c);
   r.runs.assign(n_rigs, 0);
@@ -321,6 +360,16 @@ mantis_status refine_run(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32
   r.I = I;
   r.record = p->record;
   r.cands = r.n_cand;
+  r.rec_loss = r.robust.loss;
+  for (int k = 0; robust && k < n_rigs; k++) r.h_rstats[k].loss = r.robust.loss;
+  return MANTIS_OK;
+}
+
+// the setting's checks (p: not null, loss != 0)
+mantis_status robust_check(Ctx* c, const mantis_refine_robust_params* p) {
+  if (!(p->tuning > 0) || !std::isfinite(p->tuning)) return refine_fail(c, "robust.tuning must be finite and > 0");
+  if (!(p->scale_floor > 0) || !std::isfinite(p->scale_floor))
+    return refine_fail(c, "robust.scale_floor must be finite and > 0");
   return MANTIS_OK;
 }
 
@@ -447,6 +496,70 @@ mantis_status mantis_get_refine_record(void* ctx, int32_t rig, int32_t pass, dou
       if (rows) std::memcpy(rows + 7 * k, hs[k].row, sizeof(double) * 7);
     }
   }
+  return MANTIS_OK;
+}
+
+void mantis_default_refine_robust_params(int32_t loss, mantis_refine_robust_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = sizeof(mantis_refine_robust_params);
+  p->loss = loss;
+  p->tuning = loss == rfn::kLossTukey ? 4.685 : 1.345;
+  p->scale_floor = 0.25;
+}
+
+void mantis_refine_robust_sizes(int32_t* params_bytes, int32_t* stats_bytes) {
+  if (params_bytes) *params_bytes = (int32_t)sizeof(mantis_refine_robust_params);
+  if (stats_bytes) *stats_bytes = (int32_t)sizeof(mantis_refine_robust_stats);
+}
+
+mantis_status mantis_refine_set_robust(void* ctx, const mantis_refine_robust_params* p) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c) return MANTIS_ERR_ARG;
+  if (!p) {
+    c->rf.robust = mantis_refine_robust_params{};
+    return MANTIS_OK;
+  }
+  if (p->struct_size != (int32_t)sizeof(mantis_refine_robust_params))
+    return refine_fail(c, "robust.struct_size mismatch");
+  if (p->loss < rfn::kLossNone || p->loss > rfn::kLossTukey) return refine_fail(c, "robust.loss outside 0..2");
+  if (p->loss == rfn::kLossNone) {
+    c->rf.robust = mantis_refine_robust_params{};
+    return MANTIS_OK;
+  }
+  if (mantis_status e = robust_check(c, p)) return e;
+  c->rf.robust = *p;
+  return MANTIS_OK;
+}
+
+mantis_status mantis_get_refine_robust(void* ctx, int32_t rig, mantis_refine_robust_stats* stats) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c) return MANTIS_ERR_ARG;
+  const Ctx::Refine& r = c->rf;
+  if (!stats) return refine_fail(c, "null argument");
+  if (!r.rigs || r.rec_loss == rfn::kLossNone) {
+    c->err = "refine robust: no refine call yet, or the last one ran with the robust rows off";
+    return MANTIS_ERR_STATE;
+  }
+  if (rig < 0 || rig >= r.rigs) return refine_fail(c, "robust stats: rig out of range");
+  *stats = r.h_rstats[rig];
+  return MANTIS_OK;
+}
+
+mantis_status mantis_get_refine_robust_record(void* ctx, int32_t rig, int32_t pass, uint32_t* keys, double* weights) {
+  Ctx* c = (Ctx*)ctx;
+  if (!c) return MANTIS_ERR_ARG;
+  bind_device(c);
+  const Ctx::Refine& r = c->rf;
+  if (!r.rigs || !r.record || r.rec_loss == rfn::kLossNone) {
+    c->err = "refine robust record: the last refine call kept none (robust rows on and params.record = 1)";
+    return MANTIS_ERR_STATE;
+  }
+  if (rig < 0 || rig >= r.rigs || pass < 0 || pass > r.runs[rig])
+    return refine_fail(c, "robust record: rig or pass out of range (0 .. the rig's iterations_run)");
+  const size_t ns = (size_t)r.C * r.cands, off = ((size_t)pass * r.rigs + rig) * ns;
+  if (keys && ns > 0) HIP_OK(hipMemcpy(keys, r.d_rkeys + off, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost));
+  if (weights && ns > 0) HIP_OK(hipMemcpy(weights, r.d_rweights + off, sizeof(double) * ns, hipMemcpyDeviceToHost));
   return MANTIS_OK;
 }
 

@@ -1,6 +1,7 @@
 // Stand-alone check of the line refinement's rules (mantis_amd/csrc/
 // mk_refine.h: line flags, one observation with its window over the frame
-// edges, the end of a pass, the gate and the covariance, the whole iteration)
+// edges, the end of a pass, the gate and the covariance, the whole iteration,
+// the robust rows: key, median, scale, weight, the starved gate)
 // on small synthetic frames that are allocated at exactly their size, as a
 // program of its own so that it can be built with sanitizers and run directly:
 //   g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined \
@@ -301,11 +302,142 @@ static void check_seq() {
   for (int e = 0; e < 16; e++) CHECK(std::isfinite(res.T_w_b[e]));
 }
 
+// the robust rows: keys at their limits, the lower median of 0, 1, 2 and many keys (buffers of
+// exactly n entries), both losses, t exactly 1, the starved gate, the whole iteration
+static void check_robust() {
+  const int32_t big = 31 * 195075;
+  CHECK(rf::robust_key(1, 0) == 0 && rf::robust_key(1, 15) == (15u << 20) && rf::robust_key(1, -15) == (15u << 20));
+  CHECK(rf::robust_key(big, 15 * big) == (15u << 20) && rf::robust_key(big, -15 * big) == (15u << 20));
+  CHECK(rf::robust_key(big, big) == (1u << 20) && rf::robust_key(big, -1) == 0 && rf::robust_key(3, -2) == 699050);
+  for (int loss : {rf::kLossHuber, rf::kLossTukey}) {
+    const rf::Robust rb{loss, 0, loss == rf::kLossHuber ? 1.345 : 4.685, 0.25};
+    for (int n : {0, 1, 2, 3, 8, 9, 4321}) {
+      std::vector<uint32_t> keys(n);
+      std::vector<int32_t> codes(n);
+      std::vector<double> w(n);
+      for (int k = 0; k < n; k++) {
+        keys[k] = (uint32_t)(rnd64() % (15u << 20));
+        codes[k] = (rnd64() % 4) ? 0 : 4;
+      }
+      for (int masked = 0; masked < 2; masked++) {
+        rf::RobustPass P;
+        rf::robust_weights(keys.data(), masked ? codes.data() : nullptr, n, rb, w.data(), P);
+        std::vector<uint32_t> live;
+        for (int k = 0; k < n; k++)
+          if (!masked || codes[k] == 0) live.push_back(keys[k]);
+        std::sort(live.begin(), live.end());
+        CHECK(P.n_obs == (int)live.size());
+        CHECK(P.median_key == (live.empty() ? 0u : live[(live.size() - 1) / 2]));
+        CHECK(P.scale == rf::robust_scale(P.median_key, 0.25) && P.scale >= 0.25);
+        int down = 0, zero = 0;
+        double sum = 0;
+        for (int k = 0; k < n; k++) {
+          if (masked && codes[k]) {
+            CHECK(w[k] == 0.0);
+            continue;
+          }
+          CHECK(w[k] >= 0.0 && w[k] <= 1.0);
+          down += w[k] < 1.0;
+          zero += w[k] == 0.0;
+          sum += w[k];
+        }
+        CHECK(down == P.n_down && zero == P.n_zero && sum == P.sum_w);
+        if (loss == rf::kLossHuber) CHECK(P.n_zero == 0);
+      }
+      // all keys equal: the median is that key and every row weighs the same
+      std::fill(keys.begin(), keys.end(), 5u << 20);
+      rf::RobustPass P;
+      rf::robust_weights(keys.data(), nullptr, n, rb, w.data(), P);
+      CHECK(P.median_key == (n ? 5u << 20 : 0u));
+      for (int k = 1; k < n; k++) CHECK(w[k] == w[0]);
+      if (n) CHECK(w[0] == (loss == rf::kLossHuber ? 1.0 : rf::robust_weight(5u << 20, rb, 1.4826 * 5.0)) && w[0] > 0);
+    }
+    // t exactly 1: tuning 2 on a scale of 0.5
+    const rf::Robust one{loss, 0, 2.0, 0.5};
+    CHECK(rf::robust_weight(1u << 20, one, 0.5) == (loss == rf::kLossHuber ? 1.0 : 0.0));
+    CHECK(rf::robust_weight((1u << 20) - 1, one, 0.5) > 0.0 && rf::robust_weight((1u << 20) + 1, one, 0.5) < 1.0);
+    CHECK(rf::robust_weight(0, one, 0.5) == 1.0);
+  }
+  // the starved gate: rows enough, positive weights too few
+  double acc[28] = {0};
+  for (int k = 0; k < 20; k++) {
+    double row[7] = {0, 0, 0, 0, 0, 0, 0.01};
+    row[k % 6] = 1.0;
+    rf::accumulate_row(row, acc);
+  }
+  mantis_refine_result R{};
+  for (int e = 0; e < 16; e++) R.T_w_b[e] = (e % 5 == 0) ? 1.0 : 0.0;
+  CHECK(rf::end_pass_robust(acc, 20, 11, 0, 4, 12, 0.0, R) && R.status == rf::kStarved && R.n_obs[0] == 20);
+  CHECK(R.rms[0] == std::sqrt(acc[27] / 20.0) && R.iterations_run == 0 && R.T_w_b[3] == 0.0);
+  R.status = rf::kOk;
+  CHECK(!rf::end_pass_robust(acc, 20, 12, 0, 4, 12, 0.0, R) && R.status == rf::kOk && R.iterations_run == 1);
+  CHECK(rf::end_pass_robust(acc, 20, 0, 4, 4, 12, 0.0, R) && R.status == rf::kOk);  // the final pass starves nothing
+
+  // the whole iteration on check_seq's painted grid, three cameras of which one sees a grid painted from another pose
+  const int W = 320, H = 240;
+  const mk::Cam cam{150.0, 150.0, 159.5, 119.5, {0.003, -0.01, 0.005, -0.002}};
+  const double pitch = 0.08;
+  std::vector<double> X;
+  for (int j = -4; j <= 4; j += 2)
+    for (int i = -8; i <= 8; i++) {
+      X.insert(X.end(), {i * pitch * 0.5, j * pitch, 0.0});
+      if (i % 4) X.insert(X.end(), {j * pitch, i * pitch * 0.5, 0.0});
+    }
+  const int n = (int)X.size() / 3;
+  std::vector<uint8_t> flags(n);
+  rf::line_flags(X.data(), n, pitch * 0.5, flags.data());
+  std::vector<int32_t> cand(n);
+  const int nc = rf::candidates(flags.data(), n, cand.data());
+  double T[16], Tbad[16], T0[16];
+  nadir_pose(0.03, -0.02, 0.6, 0.3, T);
+  nadir_pose(0.03, -0.02 + 0.006, 0.6, 0.3 + 0.004, Tbad);
+  nadir_pose(0.034, -0.024, 0.6, 0.304, T0);
+  std::vector<uint8_t> img((size_t)W * H * 3, 0), bad((size_t)W * H * 3, 0);
+  paint_grid(img, W, H, T, cam, 2 * pitch, 2, 4 * pitch);
+  paint_grid(bad, W, H, Tbad, cam, 2 * pitch, 2, 4 * pitch);
+  const uint8_t* frames[3] = {img.data(), img.data(), bad.data()};
+  const mk::GnCam gcs[3] = {identity_cam(), identity_cam(), identity_cam()};
+  const mk::Cam cams[3] = {cam, cam, cam};
+  mantis_refine_params p{};
+  p.struct_size = sizeof(p);
+  p.iterations = 5;
+  p.half_window = 6;
+  p.white_thresh = 3 * 64 * 64;
+  p.min_weight = 12288;
+  p.min_obs = 12;
+  p.landmark_pitch = pitch * 0.5;
+  mantis_refine_result plain, off;
+  rf::refine_seq(T0, gcs, cams, frames, 3, W, H, X.data(), n, 0, cand.data(), nc, p, plain, nullptr);
+  mantis_refine_robust_stats st;
+  rf::refine_seq_robust(T0, gcs, cams, frames, 3, W, H, X.data(), n, 0, cand.data(), nc, p, rf::Robust{0, 0, 1.0, 1.0}, off,
+                        &st);
+  CHECK(std::memcmp(&plain, &off, sizeof(plain)) == 0 && st.loss == 0 && st.n_down[0] == 0);
+  const double d0 = std::hypot(plain.T_w_b[3] - T[3], plain.T_w_b[7] - T[7]);
+  for (int loss : {rf::kLossHuber, rf::kLossTukey}) {
+    mantis_refine_result res;
+    rf::refine_seq_robust(T0, gcs, cams, frames, 3, W, H, X.data(), n, 0, cand.data(), nc, p,
+                          rf::Robust{loss, 0, loss == rf::kLossHuber ? 1.345 : 4.685, 0.25}, res, &st);
+    const double d1 = std::hypot(res.T_w_b[3] - T[3], res.T_w_b[7] - T[7]);
+    const int fp = res.iterations_run;
+    std::printf("robust loss %d: status %d runs %d n_obs %d down %d zero %d scale %.3f  plain %.5f -> %.5f m\n", loss,
+                res.status, fp, res.n_obs[fp], st.n_down[fp], st.n_zero[fp], st.scale[fp], d0, d1);
+    CHECK(res.status == rf::kOk && fp == 5 && st.loss == loss && st.n_down[fp] > 0 && st.sum_w[fp] < res.n_obs[fp]);
+    CHECK(d1 < d0);
+    for (int k = fp + 1; k < 11; k++) CHECK(st.median_key[k] == 0 && st.scale[k] == 0.0 && st.sum_w[k] == 0.0);
+  }
+  // no candidates at all: every pass is empty, the stats are defined
+  mantis_refine_result res;
+  rf::refine_seq_robust(T0, gcs, cams, frames, 3, W, H, X.data(), n, 0, cand.data(), 0, p, rf::Robust{2, 0, 4.685, 0.25},
+                        res, &st);
+  CHECK(res.status == rf::kStarved && st.median_key[0] == 0 && st.scale[0] == 0.25 && st.sum_w[0] == 0.0);
+}
+
 int main() {
   check_flags();
   check_windows();
   check_passes();
   check_seq();
+  check_robust();
   if (g_fail) {
     std::printf("refinecheck: %d failure(s)\n", g_fail);
     return 1;
