@@ -965,6 +965,116 @@ void mantis_mcl_refine_sizes(int32_t* mode_bytes, int32_t* refined_bytes);
 mantis_status mantis_mcl_refine_modes(void* ctx, const mantis_image* cams, int32_t n_cams, int32_t max_modes,
                                       const mantis_refine_params* p, int32_t apply, struct mantis_mcl_refined* out);
 
+/* ---- Extrinsic calibration: joint poses + camera extrinsics on the lines ----
+ * Every refine entry above takes mantis_image.T_base_cam as exact. This call
+ * estimates it: from N views of one rig (N x C frames, the rig standing at N
+ * places) it runs a joint Gauss-Newton over the N base poses and the
+ * extrinsics of the cameras named in `free_cams`, on the grid lines, and
+ * returns all of them with a covariance per free camera. All addition: no
+ * other entry point, struct, kernel result or draw changes, MANTIS_ABI_VERSION
+ * stays 5 (find the entries by name, check the sizes with mantis_calib_sizes).
+ * The caller's mantis_images are never written; the context's prior, cv::RNG
+ * state and robust setting (mantis_refine_set_robust) are neither read nor
+ * changed. Robust rows do not apply here: a drifted camera is modelled, not
+ * down-weighted.
+ *
+ * Unknowns and the gauge. T_r = T_w_b of view r < N, and E_c = T_base_cam of
+ * camera c for every bit c set in free_cams. At least one camera must be held
+ * (not free) and at least one free: that fixes the gauge, and implies C >= 2.
+ * The nominal extrinsic of camera c is read from view 0's cams[c].T_base_cam.
+ *
+ * One observation of (view r, camera c, candidate i) is exactly steps 1-8 of
+ * the line refinement above (same candidates, window, codes, Sw, Skw,
+ * residual), with R_cb / t_cb = inverse(E_c as currently estimated). The
+ * slot's row has 13 entries [J_pose (6) | J_ext (6) | r]: J_pose is the
+ * refinement's [-h | h [q]x]; J_ext belongs to the right perturbation E_c <-
+ * E_c D(eps), D the update matrix of the refinement's step (Rodrigues rotation
+ * eps[3..5], translation eps[0..2] taken as is): J_ext = [-g | g [p]x] with
+ * g = nh^T Jpi and p the point in the camera frame (step 1). J_ext is six
+ * zeros for a held camera; a rejected slot is thirteen zeros. Slot index =
+ * c n_cand + candidate inside a view, no compaction.
+ *
+ * A pass's accumulators. Per (view, camera): acc91 = the upper triangle, row
+ * by row, of M^T M for M = [J_pose | J_ext | r] (blocks PP, PE, Pr, EE, Er,
+ * rr), and the count of code-0 rows. n_obs_cam[c] (over the views) and n_obs
+ * are integer sums; rms = sqrt(sum rr / n_obs), the sum in (view, camera)
+ * order (0 when n_obs = 0).
+ *
+ * The end of pass k < I:
+ *  1. STARVED (1) if some view has fewer than min_obs rows over its cameras
+ *     (mantis_refine_params.min_obs is per view here), or some free camera
+ *     fewer than min_obs_cam rows over the views.
+ *  2. per view: A_r = sum_c PP_rc + lambda I, a_r = sum_c Pr_rc (camera order).
+ *  3. Cholesky of A_r (the refinement's loop); not positive definite:
+ *     SINGULAR (2). Y_r = A_r^-1 [E_r | a_r], E_r = the PE blocks of the free
+ *     cameras side by side in ascending camera order.
+ *  4. per free camera f: B_f = sum_r EE_rf + lambda I, b_f = sum_r Er_rf.
+ *  5. S = B - sum_r E_r^T A_r^-1 E_r, s = -b + sum_r E_r^T A_r^-1 a_r, every
+ *     sum in view order; S is at most 42 x 42.
+ *  6. left-looking Cholesky of S's lower triangle; not positive definite:
+ *     SINGULAR. eps = S^-1 s.
+ *  7. delta_r = -(Y_r's last column + Y_r's other columns x eps)
+ *     = -A_r^-1 (a_r + E_r eps).
+ *  8. T_r <- T_r D(delta_r), E_c <- E_c D(eps_c).
+ * I iterations are I + 1 observation passes; the last solves nothing. I = 0
+ * returns every input pose and extrinsic bit for bit. A stop ends the whole
+ * call; the results keep the figures of the pass that stopped it
+ * (iterations_run = the steps taken; entries past it are 0).
+ *
+ * Gate and covariance (host). dof = n_obs - 6 N - 6 F (F free cameras).
+ * calibrated = status OK && no starved gate on the final pass && (max_rms <= 0
+ * || final rms <= max_rms) && dof > 0 && S of the final pass with lambda = 0
+ * positive definite. covariance[c] = (r^T r / dof) (S^-1)_cc for a free camera
+ * c -- the marginal over the poses -- in the order of eps (x, y, z, rot-x,
+ * rot-y, rot-z of the right perturbation), row-major; zeros for a held camera
+ * and when calibrated = 0. rms_cam[c] = sqrt(sum_r rr_rc / n_obs_cam[c]) of
+ * the final pass: the figure that names a drifted camera. */
+typedef struct mantis_calib_params {
+  int32_t struct_size;   /* sizeof(mantis_calib_params) */
+  int32_t free_cams;     /* bit c: camera c's extrinsic is unknown */
+  int32_t min_obs_cam;   /* >= 6 */
+  int32_t pad;
+} mantis_calib_params;
+/* free_cams 0 (the caller names them) / min_obs_cam 60 */
+void mantis_default_calib_params(mantis_calib_params* p);
+
+typedef struct mantis_calib_result {
+  int32_t status, calibrated, iterations_run, n_cand; /* status: 0 OK, 1 STARVED, 2 SINGULAR */
+  int32_t n_rigs, n_cams, free_cams, pad;
+  double T_base_cam[8][16];   /* the extrinsics, row-major; the input bytes for held cameras; zeros past n_cams */
+  int32_t n_obs[11];          /* per pass */
+  int32_t pad2;
+  int32_t n_obs_cam[11][8];
+  double rms[11];
+  double rms_cam[8];          /* of the final pass */
+  double delta_cam[10][8][6]; /* eps per pass and camera; zeros for held cameras */
+  double covariance[8][36];
+} mantis_calib_result;
+/* sizeof(mantis_calib_params), sizeof(mantis_calib_result) (host only) */
+void mantis_calib_sizes(int32_t* params_bytes, int32_t* result_bytes);
+
+/* n_rigs views of one rig of cams_per_rig cameras (cams[r * cams_per_rig + c]
+ * as in mantis_refine_batch), view r starting from T_w_b_in[r] (n_rigs x 16).
+ * The window, gates, lambda, pitch, iterations and `record` come from p.
+ * T_w_b_out (n_rigs x 16) gets the views' poses, out the rest. Limits and
+ * errors as mantis_refine_batch, and MANTIS_ERR_ARG (nothing launched;
+ * mantis_last_error names the field) for: n_rigs > 256, cams_per_rig < 2,
+ * free_cams empty, free_cams naming every camera, free_cams with a bit at or
+ * above cams_per_rig, min_obs_cam < 6, a T_base_cam that is not finite, a
+ * view whose cams[c].T_base_cam differs from view 0's in any byte. Device
+ * work: 3 (I + 1) launches on the context stream (k_calib_obs, k_calib_rig,
+ * k_calib_solve per pass), then the copies of the results. */
+mantis_status mantis_calibrate_extrinsics(void* ctx, const mantis_image* cams, int32_t n_rigs, int32_t cams_per_rig,
+                                          const double* T_w_b_in, const mantis_refine_params* p,
+                                          const mantis_calib_params* cp, double* T_w_b_out, mantis_calib_result* out);
+/* Record of view `rig`, pass 0 .. iterations_run, of the last calibration made
+ * with p->record = 1; each pointer nullable: T_w_b (16) and T_base_cam (C x
+ * 16) the pass observed at; per slot (C x n_cand) codes, Sw, Skw and rows (13
+ * doubles each); acc91 (C x 91) of the view. MANTIS_ERR_STATE: no such record.
+ * MANTIS_ERR_ARG: rig or pass out of range. */
+mantis_status mantis_get_calib_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, double* T_base_cam,
+                                      int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, double* acc91);
+
 #ifdef __cplusplus
 }
 #endif

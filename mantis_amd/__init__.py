@@ -134,6 +134,18 @@ class MantisMclRefined(C.Structure):
                 ("modes", MantisMclModes), ("mode", MantisMclModeRefined * 8)]
 
 
+class MantisCalibParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("free_cams", C.c_int32), ("min_obs_cam", C.c_int32), ("pad", C.c_int32)]
+
+
+class MantisCalibResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("calibrated", C.c_int32), ("iterations_run", C.c_int32), ("n_cand", C.c_int32),
+                ("n_rigs", C.c_int32), ("n_cams", C.c_int32), ("free_cams", C.c_int32), ("pad", C.c_int32),
+                ("T_base_cam", (C.c_double * 16) * 8), ("n_obs", C.c_int32 * 11), ("pad2", C.c_int32),
+                ("n_obs_cam", (C.c_int32 * 8) * 11), ("rms", C.c_double * 11), ("rms_cam", C.c_double * 8),
+                ("delta_cam", ((C.c_double * 6) * 8) * 10), ("covariance", (C.c_double * 36) * 8)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -270,6 +282,12 @@ _SIGS = {
     "mantis_refine_set_robust": (C.c_int, [C.c_void_p, C.POINTER(MantisRefineRobustParams)]),
     "mantis_get_refine_robust": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MantisRefineRobustStats)]),
     "mantis_get_refine_robust_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mantis_default_calib_params": (None, [C.POINTER(MantisCalibParams)]),
+    "mantis_calib_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_calibrate_extrinsics": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32, C.c_void_p,
+                                              C.POINTER(MantisRefineParams), C.POINTER(MantisCalibParams), C.c_void_p,
+                                              C.POINTER(MantisCalibResult)]),
+    "mantis_get_calib_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "mantis_mcl_refine_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mantis_mcl_refine_modes": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32,
                                           C.POINTER(MantisRefineParams), C.c_int32, C.POINTER(MantisMclRefined)]),
@@ -666,6 +684,62 @@ class Mantis:
         f = np.zeros(n, np.uint8)
         self._chk(lib().mantis_refine_line_flags(self.h, float(pitch), f.ctypes.data, n), "refine_line_flags")
         return f
+
+    # extrinsic calibration (mantis_calibrate_extrinsics, include/mantis.h) ----
+    def calib_params(self, free_cams, **params):
+        """mantis_default_calib_params with `free_cams` (a bit mask or an iterable of camera indices)."""
+        p = MantisCalibParams()
+        lib().mantis_default_calib_params(C.byref(p))
+        if not isinstance(free_cams, int):
+            free_cams = sum(1 << int(c) for c in free_cams)
+        p.free_cams = free_cams
+        for k, v in params.items():
+            if k != "min_obs_cam":
+                raise TypeError(f"calib: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def calibrate_extrinsics(self, images, views, T_in, free_cams, min_obs_cam=None, **refine_params):
+        """mantis_calibrate_extrinsics: `views` views of one rig (images
+        view-major, every view with the rig's nominal T_base_cam) from the base
+        poses T_in (views x 4 x 4); `free_cams` names the cameras whose
+        extrinsics are unknown. Returns (T_w_b [views, 4, 4], MantisCalibResult)."""
+        n = len(images)
+        assert views > 0 and n % views == 0
+        cams = (MantisImage * n)(*images)
+        T = np.ascontiguousarray(T_in, np.float64).reshape(-1)
+        assert T.size == 16 * views
+        p = self.refine_params(**refine_params)
+        cp = self.calib_params(free_cams, **({} if min_obs_cam is None else {"min_obs_cam": min_obs_cam}))
+        T_out = np.zeros((views, 4, 4))
+        out = MantisCalibResult()
+        self._chk(lib().mantis_calibrate_extrinsics(self.h, cams, views, n // views, T.ctypes.data, C.byref(p),
+                                                    C.byref(cp), T_out.ctypes.data, C.byref(out)),
+                  "calibrate_extrinsics")
+        self._calib_shape = (n // views, out.n_cand)
+        return T_out, out
+
+    def calib_record(self, rig, pass_):
+        """Pass `pass_` (0 .. iterations_run) of view `rig` of the last
+        calibration made with record=1 (mantis_get_calib_record): (T_w_b
+        [4, 4], T_base_cam [C, 4, 4], codes, Sw, Skw [slots] int32, rows
+        [slots, 13], acc91 [C, 91]); slot = camera x n_cand + candidate."""
+        shape = getattr(self, "_calib_shape", None)
+        if shape is None:
+            raise MantisError("calib_record: no calibration on this context")
+        Cn, nc = shape
+        ns = Cn * nc
+        T = np.zeros((4, 4))
+        E = np.zeros((Cn, 4, 4))
+        codes = np.zeros(ns, np.int32)
+        Sw = np.zeros(ns, np.int32)
+        Skw = np.zeros(ns, np.int32)
+        rows = np.zeros((ns, 13))
+        acc = np.zeros((Cn, 91))
+        self._chk(lib().mantis_get_calib_record(self.h, rig, pass_, T.ctypes.data, E.ctypes.data, codes.ctypes.data,
+                                                Sw.ctypes.data, Skw.ctypes.data, rows.ctypes.data, acc.ctypes.data),
+                  "get_calib_record")
+        return T, E, codes, Sw, Skw, rows, acc
 
     # Monte Carlo localization (mantis_mcl_*, include/mantis.h) ---------------
     def mcl_params(self, **params):

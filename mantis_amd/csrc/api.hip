@@ -358,6 +358,19 @@ struct Ctx {
     size_t rslot_cap = 0;
     int rec_loss = 0;  // the last call's loss
   } rf;
+  // extrinsic calibration (calib_impl.hip): workspaces grown to the largest call
+  // (per-view buffers hold view_cap views of 8 cameras) and the last call's shape
+  // (mantis_get_calib_record)
+  struct Calib {
+    void *d_state = nullptr, *h_state = nullptr;  // CalibState; h: pinned, with the poses, accumulators and counts behind it
+    double *d_T = nullptr, *d_acc = nullptr, *d_Y = nullptr, *d_Wt = nullptr;
+    int32_t *d_cnt = nullptr, *d_pd = nullptr;
+    double *d_recT = nullptr, *d_recE = nullptr, *d_recAcc = nullptr;  // [pass][view][16], [pass][C][16], [pass][view][C][91]
+    void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
+    int view_cap = 0;
+    size_t slot_cap = 0, racc_cap = 0;
+    int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
+  } cb;
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1403,6 +1416,11 @@ mantis_status mantis_destroy(void* ctx) {
     if (p) (void)hipFree(p);
   if (c->rf.h_state) (void)hipHostFree(c->rf.h_state);
   if (c->rf.h_rstats) (void)hipHostFree(c->rf.h_rstats);
+  void* cptrs[] = {c->cb.d_state, c->cb.d_T, c->cb.d_acc, c->cb.d_Y, c->cb.d_Wt, c->cb.d_cnt, c->cb.d_pd,
+                   c->cb.d_recT, c->cb.d_recE, c->cb.d_recAcc, c->cb.d_slots};
+  for (void* p : cptrs)
+    if (p) (void)hipFree(p);
+  if (c->cb.h_state) (void)hipHostFree(c->cb.h_state);
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
                    c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes, c->mcl.h_moved};
@@ -1452,6 +1470,7 @@ mantis_status mantis_set_map(void* ctx, const double* white, int32_t nw, const d
   c->h_lm = all;
   c->rf.pitch = 0;  // the line flags of the previous map go (refine_impl.hip)
   c->rf.rigs = 0;
+  c->cb.rigs = 0;
   return MANTIS_OK;
 }
 
@@ -2257,5 +2276,6 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "mcl_modes_impl.hip"
 #include "mcl_color_impl.hip"
 #include "refine_impl.hip"
+#include "calib_impl.hip"
 #include "mcl_refine_impl.hip"
 #include "ros_wire.h"

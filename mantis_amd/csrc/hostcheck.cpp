@@ -13,6 +13,7 @@
 static int g_jacobi_ff = 1;
 #define MK_JACOBI_FF g_jacobi_ff
 #include "mk_bits.h"
+#include "mk_calib.h"
 #include "mk_contour.h"
 #include "mk_gn.h"
 #include "mk_math.h"
@@ -657,6 +658,71 @@ int hc_refine_end_pass_robust(const double* acc28, int n_obs, int n_pos, int pas
 }
 int hc_sizeof_refine_robust_params(void) { return (int)sizeof(mantis_refine_robust_params); }
 int hc_sizeof_refine_robust_stats(void) { return (int)sizeof(mantis_refine_robust_stats); }
+
+// Extrinsic calibration (mk_calib.h): the rules k_calib_obs / k_calib_rig / k_calib_solve run.
+// hc_refine_obs with rows of 13 ([J_pose | J_ext | r]; J_ext zeros unless free_cam)
+int hc_calib_obs(const double* Twb, const double* Tbc, const double* K, const double* D, const uint8_t* bgr, int W,
+                 int H, const double* X, int nw, int nr, int ng, const uint8_t* flags, int R, int white_thresh,
+                 int min_weight, int free_cam, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, int32_t* tie) {
+  namespace rf = mk::refine;
+  const int n = nw + nr + ng;
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags, n, cand.data());
+  mk::GnCam gc;
+  rf::gncam_from(Tbc, gc);
+  const mk::Cam cm = hc_cam(K, D);
+  double Rt[9], t[3];
+  rf::pose_parts(Twb, Rt, t);
+  const rf::Window win{R, white_thresh, min_weight, 0};
+  for (int k = 0; k < nc; k++) {
+    const int i = cand[k] & 0xffff, axis = cand[k] >> 16;
+    int tg[3], near = 0;
+    rf::target_bgr(i, nw, nr, tg);
+    mk::calib::Slot o;
+    mk::calib::observe(Rt, t, gc, cm, bgr, W, H, X + 3 * i, axis, tg, win, free_cam != 0, o, &near);
+    codes[k] = o.code;
+    Sw[k] = o.Sw;
+    Skw[k] = o.Skw;
+    std::memcpy(rows + 13 * k, o.row, sizeof(o.row));
+    if (tie) tie[k] = near;
+  }
+  return nc;
+}
+// acc91 of n rows of 13 doubles, summed in row order
+void hc_calib_accumulate(const double* rows, int n, double* acc91) {
+  for (int e = 0; e < mk::calib::kAcc; e++) acc91[e] = 0.0;
+  for (int k = 0; k < n; k++) mk::calib::accumulate_row(rows + 13 * k, acc91);
+}
+// the end of a pass from given accumulators (N x C x 91) and counts (N x C): T (N x 16, in / out),
+// R->T_base_cam (in / out), delta (N x 6, nullable). Returns 1 when the call is finished.
+int hc_calib_end_pass(const double* acc91, const int32_t* cnt, int N, int C, int free_cams, int pass, int I, int min_obs,
+                      int min_obs_cam, double lambda, double* T, mantis_calib_result* R, double* delta) {
+  return mk::calib::end_pass(acc91, cnt, N, C, (uint32_t)free_cams, pass, I, min_obs, min_obs_cam, lambda, T, *R, delta)
+             ? 1 : 0;
+}
+// the whole call on the host: N views of C cameras (Tbc C x 16, K C x 9, D C x 4, frames: N x C
+// pointers to W x H frames of stride 3 W), rows summed in slot order
+void hc_calib_seq(const double* T_in, const double* Tbc, const double* K, const double* D, const uint8_t* const* frames,
+                  int N, int C, int W, int H, const double* X, int nw, int nr, int ng, const mantis_refine_params* p,
+                  const mantis_calib_params* cp, double* T_out, mantis_calib_result* out) {
+  namespace rf = mk::refine;
+  const int n = nw + nr + ng;
+  std::vector<uint8_t> flags(n > 0 ? n : 1);
+  rf::line_flags(X, n, p->landmark_pitch, flags.data());
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags.data(), n, cand.data());
+  std::vector<mk::Cam> cm(C);
+  for (int c = 0; c < C; c++) cm[c] = hc_cam(K + 9 * c, D + 4 * c);
+  mk::calib::calib_seq(T_in, Tbc, cm.data(), frames, N, C, W, H, X, nw, nr, cand.data(), nc, *p, *cp, T_out, *out,
+                       nullptr);
+}
+// the gate, rms_cam and the covariances (calib::conclude) of a result record with the last pass's acc91 / counts
+void hc_calib_conclude(const double* acc91, const int32_t* cnt, int N, int C, int free_cams, int min_obs,
+                       int min_obs_cam, double max_rms, mantis_calib_result* R) {
+  mk::calib::conclude(acc91, cnt, N, C, (uint32_t)free_cams, min_obs, min_obs_cam, max_rms, *R);
+}
+int hc_sizeof_calib_params(void) { return (int)sizeof(mantis_calib_params); }
+int hc_sizeof_calib_result(void) { return (int)sizeof(mantis_calib_result); }
 
 // The modes refined (mk_mcl_refine.h): the rules mantis_mcl_refine_modes and k_mcl_recentre run.
 // modes: a struct mantis_mcl_modes; T_ref 8 x 16 (row-major), refined 8; out: key_kept / applied (8

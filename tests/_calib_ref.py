@@ -1,0 +1,259 @@
+"""Extrinsic calibration, test side: ctypes bindings of the host build's
+hc_calib_* (mantis_amd/csrc/mk_calib.h through build/libmantis_hostcheck.so),
+the full normal system of include/mantis.h assembled in numpy, and the scenes
+the CPU and GPU tests share.
+"""
+import ctypes as C
+import functools
+
+import numpy as np
+
+import _refine_ref as RR
+import _refine_robust_ref as RB
+from mantis_amd import synth
+
+ACC = 91
+TRI = np.triu_indices(13)
+
+
+def hc():
+    import mantis_amd as M
+
+    L = RR.hc()
+    vp = C.c_void_p
+    L.hc_calib_obs.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                               C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    L.hc_calib_obs.restype = C.c_int
+    L.hc_calib_accumulate.argtypes = [vp, C.c_int, vp]
+    L.hc_calib_accumulate.restype = None
+    L.hc_calib_end_pass.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                    vp, C.POINTER(M.MantisCalibResult), vp]
+    L.hc_calib_end_pass.restype = C.c_int
+    L.hc_calib_seq.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int,
+                               C.POINTER(M.MantisRefineParams), C.POINTER(M.MantisCalibParams), vp,
+                               C.POINTER(M.MantisCalibResult)]
+    L.hc_calib_seq.restype = None
+    L.hc_calib_conclude.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                    C.POINTER(M.MantisCalibResult)]
+    L.hc_calib_conclude.restype = None
+    L.hc_sizeof_calib_params.restype = C.c_int
+    L.hc_sizeof_calib_result.restype = C.c_int
+    return L
+
+
+def calib_params(free_cams, min_obs_cam=None):
+    import mantis_amd as M
+
+    p = M.MantisCalibParams()
+    M.lib().mantis_default_calib_params(C.byref(p))
+    p.free_cams = free_cams
+    if min_obs_cam is not None:
+        p.min_obs_cam = min_obs_cam
+    return p
+
+
+def obs(T, Tbc, K, D, img, X, nw, nr, ng, f, free_cam, R=12, white_thresh=12288, min_weight=24576):
+    """hc_calib_obs: (codes, Sw, Skw, rows [n_cand, 13], tie [n_cand]) of one pass for one camera."""
+    T = np.ascontiguousarray(T, np.float64)
+    Tbc = np.ascontiguousarray(Tbc, np.float64)
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    D = np.ascontiguousarray(D, np.float64).reshape(4)
+    img = np.ascontiguousarray(img, np.uint8)
+    h, w = img.shape[:2]
+    f = np.ascontiguousarray(f, np.uint8)
+    nc = len(RR.candidates(f))
+    codes = np.zeros(nc, np.int32)
+    Sw = np.zeros(nc, np.int32)
+    Skw = np.zeros(nc, np.int32)
+    rows = np.zeros((nc, 13))
+    tie = np.zeros(nc, np.int32)
+    got = hc().hc_calib_obs(T.ctypes.data, Tbc.ctypes.data, K.ctypes.data, D.ctypes.data, img.ctypes.data, w, h,
+                            X.ctypes.data, nw, nr, ng, f.ctypes.data, R, white_thresh, min_weight, int(bool(free_cam)),
+                            codes.ctypes.data, Sw.ctypes.data, Skw.ctypes.data, rows.ctypes.data, tie.ctypes.data)
+    assert got == nc
+    return codes, Sw, Skw, rows, tie
+
+
+def accumulate(rows):
+    rows = np.ascontiguousarray(rows, np.float64).reshape(-1, 13)
+    acc = np.zeros(ACC)
+    hc().hc_calib_accumulate(rows.ctypes.data, len(rows), acc.ctypes.data)
+    return acc
+
+
+def np_acc91(rows):
+    """(the upper triangle of M^T M in numpy sums, the bound of those sums' own rounding error:
+    n 2^-53 |M|^T |M|, the textbook bound of a float64 dot product of n terms)."""
+    M = np.asarray(rows, np.float64).reshape(-1, 13)
+    return (M.T @ M)[TRI], (len(M) * 2.0 ** -53 * (np.abs(M).T @ np.abs(M)))[TRI]
+
+
+def pass_acc(Ts, exts, frames, lm, free_cams, p, K=None, D=None):
+    """One observation pass on the host: (acc91 [N, C, 91], cnt [N, C]) at the poses Ts and extrinsics exts."""
+    X, nw, nr, ng = lm
+    N, Cn = len(Ts), len(exts)
+    h, w = frames[0][0].shape[:2]
+    if K is None:
+        K, D = synth.intrinsics(w, h)
+    f = RR.flags(X, p.landmark_pitch)
+    acc = np.zeros((N, Cn, ACC))
+    cnt = np.zeros((N, Cn), np.int32)
+    for r in range(N):
+        for c in range(Cn):
+            codes, _, _, rows, _ = obs(Ts[r], exts[c], K, D, frames[r][c], X, nw, nr, ng, f, free_cams >> c & 1,
+                                       R=p.half_window, white_thresh=p.white_thresh, min_weight=p.min_weight)
+            acc[r, c] = accumulate(rows)
+            cnt[r, c] = int((codes == 0).sum())
+    return acc, cnt
+
+
+def new_result(exts, free_cams, N, n_cand=0):
+    import mantis_amd as M
+
+    R = M.MantisCalibResult()
+    R.n_cand, R.n_rigs, R.n_cams, R.free_cams = n_cand, N, len(exts), free_cams
+    for c, e in enumerate(exts):
+        for k, v in enumerate(np.asarray(e, np.float64).reshape(16)):
+            R.T_base_cam[c][k] = v
+    return R
+
+
+def end_pass(acc, cnt, free_cams, pass_, I, p, cp, Ts, R):
+    """hc_calib_end_pass on R (in / out): (finished, T_next [N, 4, 4], delta [N, 6])."""
+    acc = np.ascontiguousarray(acc, np.float64)
+    cnt = np.ascontiguousarray(cnt, np.int32)
+    N, Cn = cnt.shape
+    T = np.ascontiguousarray(np.array(Ts, np.float64).reshape(N, 16)).copy()
+    d = np.zeros((N, 6))
+    fin = hc().hc_calib_end_pass(acc.ctypes.data, cnt.ctypes.data, N, Cn, free_cams, pass_, I, p.min_obs,
+                                 cp.min_obs_cam, p.lambda_, T.ctypes.data, C.byref(R), d.ctypes.data)
+    return bool(fin), T.reshape(N, 4, 4), d
+
+
+def conclude(acc, cnt, free_cams, p, cp, R):
+    acc = np.ascontiguousarray(acc, np.float64)
+    cnt = np.ascontiguousarray(cnt, np.int32)
+    N, Cn = cnt.shape
+    hc().hc_calib_conclude(acc.ctypes.data, cnt.ctypes.data, N, Cn, free_cams, p.min_obs, cp.min_obs_cam, p.max_rms,
+                           C.byref(R))
+
+
+def seq(T_in, exts, frames, lm, p, cp, K=None, D=None):
+    """hc_calib_seq: (T_out [N, 4, 4], MantisCalibResult). frames[r][c]."""
+    import mantis_amd as M
+
+    X, nw, nr, ng = lm
+    N, Cn = len(frames), len(exts)
+    h, w = frames[0][0].shape[:2]
+    if K is None:
+        K, D = synth.intrinsics(w, h)
+    T = np.ascontiguousarray(np.array(T_in, np.float64).reshape(N, 16))
+    E = np.ascontiguousarray(np.array(exts, np.float64).reshape(Cn, 16))
+    Ks = np.ascontiguousarray(np.tile(np.asarray(K, np.float64).reshape(9), (Cn, 1)))
+    Ds = np.ascontiguousarray(np.tile(np.asarray(D, np.float64).reshape(4), (Cn, 1)))
+    keep = [np.ascontiguousarray(frames[r][c], np.uint8) for r in range(N) for c in range(Cn)]
+    ptrs = (C.c_void_p * (N * Cn))(*[k.ctypes.data for k in keep])
+    T_out = np.zeros((N, 4, 4))
+    out = M.MantisCalibResult()
+    hc().hc_calib_seq(T.ctypes.data, E.ctypes.data, Ks.ctypes.data, Ds.ctypes.data, ptrs, N, Cn, w, h, X.ctypes.data,
+                      nw, nr, ng, C.byref(p), C.byref(cp), T_out.ctypes.data, C.byref(out))
+    return T_out, out
+
+
+def exts_of(R):
+    """The result's extrinsics: [n_cams, 4, 4]."""
+    return np.array([list(R.T_base_cam[c]) for c in range(R.n_cams)]).reshape(R.n_cams, 4, 4)
+
+
+# ---- the rule in numpy: the full (6 N + 6 F) normal system ----
+def sym13(a91):
+    G = np.zeros((13, 13))
+    G[TRI] = a91
+    return G + np.triu(G, 1).T
+
+
+def free_list(free_cams, Cn):
+    return [c for c in range(Cn) if free_cams >> c & 1]
+
+
+def np_normal(acc, free_cams, lam=0.0):
+    """(H, g): the normal matrix over [poses (6 N) | free cameras (6 F)] and the gradient J^T r."""
+    N, Cn = acc.shape[:2]
+    fl = free_list(free_cams, Cn)
+    n = 6 * N + 6 * len(fl)
+    Hm, g = np.zeros((n, n)), np.zeros(n)
+    for r in range(N):
+        P = slice(6 * r, 6 * r + 6)
+        for c in range(Cn):
+            G = sym13(acc[r, c])
+            Hm[P, P] += G[:6, :6]
+            g[P] += G[:6, 12]
+            if c in fl:
+                E = slice(6 * N + 6 * fl.index(c), 6 * N + 6 * fl.index(c) + 6)
+                Hm[P, E] += G[:6, 6:12]
+                Hm[E, P] += G[6:12, :6]
+                Hm[E, E] += G[6:12, 6:12]
+                g[E] += G[6:12, 12]
+    return Hm + lam * np.eye(n), g
+
+
+# ---- scenes ----
+def true_exts(ext, cam=3):
+    """The ring's extrinsics with camera `cam` drifted (RB.drift())."""
+    e = [np.array(x) for x in ext]
+    e[cam] = RB.drift() @ e[cam]
+    return e
+
+
+def drifted_scene():
+    """Three views of the four-camera rig with camera 3 rendered through drift @ ext[3]:
+    {"ext" (nominal), "ext_true", "Twb", "frames" [r][c], "T0" (the truth moved by 2 cm / 1 degree)}."""
+    sc = RB.rigs4()
+    return {"ext": list(sc["ext"]), "ext_true": true_exts(sc["ext"]), "Twb": list(sc["Twb"]),
+            "frames": RB.contaminated_rigs4(), "T0": [RR.shift(T) for T in sc["Twb"]]}
+
+
+@functools.lru_cache(maxsize=None)
+def fresh_views(n=4, seed=4242, cfg=12):
+    """n fresh views through the true (drifted) extrinsics: ({"Twb", "frames" [r][c]})."""
+    sc = RB.rigs4()
+    ext = true_exts(sc["ext"])
+    rng = np.random.default_rng(seed)
+    Twb, frames = [], []
+    for r in range(n):
+        T = synth.random_base_pose(rng)
+        Twb.append(T)
+        fr = []
+        for c in range(4):
+            Twc = T @ ext[c]
+            fr.append(synth.render_host(synth.make_cam(Twc[:3, :3], Twc[:3, 3], RR.W, RR.H_),
+                                        synth.frame_seed(cfg, 1000 + 100 * r + c)))
+        frames.append(fr)
+    return {"Twb": Twb, "frames": frames}
+
+
+def accuracy_checks(T_out, R, lm, sc=None):
+    """The two accuracy conditions of the issue on a result of drifted_scene() (cameras 1-3 free, four
+    iterations): camera 3's errors below a quarter of their start, the held camera's bytes unchanged; and
+    four fresh views refined by hc_refine_seq end at less than half the distance with the calibrated
+    extrinsics than with the given ones. Returns the figures."""
+    sc = sc or drifted_scene()
+    X, nw, nr, ng = lm
+    E = exts_of(R)
+    assert R.status == 0 and R.calibrated == 1, (R.status, R.calibrated)
+    d0, a0 = RR.pose_dist(np.array(sc["ext"][3]), sc["ext_true"][3])
+    d1, a1 = RR.pose_dist(E[3], sc["ext_true"][3])
+    assert d1 < 0.25 * d0 and a1 < 0.25 * a0, (d0, a0, d1, a1)
+    assert E[0].tobytes() == np.ascontiguousarray(sc["ext"][0], np.float64).tobytes()
+    fv = fresh_views()
+    p = RR.default_params()
+    ratios = []
+    for r in range(len(fv["Twb"])):
+        T, T0 = fv["Twb"][r], RR.shift(fv["Twb"][r])
+        given = RR.seq(T0, sc["ext"], fv["frames"][r], X, nw, nr, ng, p)
+        calib = RR.seq(T0, list(E), fv["frames"][r], X, nw, nr, ng, p)
+        dg = RR.pose_dist(np.array(given.T_w_b).reshape(4, 4), T)[0]
+        dc = RR.pose_dist(np.array(calib.T_w_b).reshape(4, 4), T)[0]
+        assert calib.refined == 1 and dc < 0.5 * dg, (r, dg, dc)
+        ratios.append((dg, dc))
+    return {"cam3": (d0, a0, d1, a1), "fresh": ratios}
