@@ -298,7 +298,8 @@ mantis_status mantis_quad_gn(void* ctx, const double* img_pts, const double* obj
  * reference's best-1 choice keeps). Hypothesis k of this call has global index
  * index_base + k. With use_comm (after mantis_comm_init) every rank passes its
  * shard and one ncclAllGather of (err, index) pairs gives all ranks the global
- * winner. best_idx = -1 when no hypothesis was scored. */
+ * winner. best_idx = -1 when no hypothesis was scored (n == 0 on every rank);
+ * hypotheses that all see nothing tie at DBL_MAX and give the first index. */
 mantis_status mantis_score_argmin(void* ctx, const mantis_image* img, const uint8_t* mask, const double* c2w,
                                   int32_t n, int64_t index_base, int32_t use_comm, double* best_err,
                                   int64_t* best_idx);

@@ -3,7 +3,8 @@
 // against the 720 map.yaml landmarks with the fast evaluator
 // (evaluateHypotheses, HypothesisEvaluation.h:31-41, 71-158; one wave per
 // hypothesis, k_score_api), reduced on the device to the lowest error with
-// the first index on ties (the strict "<" of the reference's best-1 choice).
+// the first index on ties (the strict "<" of the reference's best-1 choice;
+// also when every error is DBL_MAX: index -1 only when n == 0).
 // Sharded over ranks: every rank scores a contiguous block of the global
 // hypothesis list; one ncclAllGather of (err, global index) per rank (16 B)
 // and the same first-minimum rule give every rank the global winner. Included
@@ -21,7 +22,10 @@ __global__ __launch_bounds__(1024) void k_argmin(const double* __restrict__ err,
   int bi = 0x7fffffff;
   for (int i = t; i < n; i += 1024) {
     const double e = err[i];
-    if (e < be) { be = e; bi = i; }  // strided scan: ascending i within a thread
+    // strided scan: ascending i within a thread. A thread's first element is
+    // taken whatever its error (wave_argmin's seed): hypotheses that all score
+    // DBL_MAX still yield the first index, and -1 is left to n == 0
+    if (e < be || bi == 0x7fffffff) { be = e; bi = i; }
   }
   se[t] = be;
   si[t] = bi;
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(1024) void k_argmin_batch(const DenseJob* __restric
   int bi = 0x7fffffff;
   for (int i = t; i < J.n; i += 1024) {
     const double e = err[J.err_off + i];
-    if (e < be) { be = e; bi = i; }
+    if (e < be || bi == 0x7fffffff) { be = e; bi = i; }  // as k_argmin
   }
   se[t] = be;
   si[t] = bi;

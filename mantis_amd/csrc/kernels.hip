@@ -4707,10 +4707,15 @@ struct WaveLms {
     lb = lb_;
     le = le_;
     const int lane = threadIdx.x & 63;
+    // an empty slice (lb == le, e.g. wave 0's half of a one-landmark map) has
+    // no last element: le - 1 is one before it, -1 when lb == 0. Its lanes read
+    // entry 0 instead; sums() takes no trip over an empty slice, so the value
+    // is never used
+    const int last = le > lb ? le - 1 : 0;
 #pragma unroll
     for (int k = 0; k < U; k++) {
       const int l = lb + lane + 64 * k;
-      L[k] = lmf[l < le ? l : le - 1];
+      L[k] = lmf[l < le ? l : last];
     }
   }
   template <class MK>

@@ -54,10 +54,14 @@ struct Cam {
 };
 Cam make_cam(const double* K, const double* D) {
   Cam c;
-  c.fx = (double)(float)K[0];
-  c.fy = (double)(float)K[4];
-  c.cx = (double)(float)K[2];
-  c.cy = (double)(float)K[5];
+  // the rounding goes through memory: written as (double)(float)K[i], g++ 11
+  // at -O3 pairs the four conversions in orc_distort and drops them, so that
+  // entry projected with the unrounded K (tests/test_score_matrix_host.py)
+  volatile float f[4] = {(float)K[0], (float)K[4], (float)K[2], (float)K[5]};
+  c.fx = (double)f[0];
+  c.fy = (double)f[1];
+  c.cx = (double)f[2];
+  c.cy = (double)f[3];
   for (int i = 0; i < 4; i++) c.k[i] = D[i];
   return c;
 }
