@@ -1076,6 +1076,131 @@ mantis_status mantis_calibrate_extrinsics(void* ctx, const mantis_image* cams, i
 mantis_status mantis_get_calib_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, double* T_base_cam,
                                       int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, double* acc91);
 
+/* ---- Intrinsic calibration: joint poses + K and fisheye D on the lines ----
+ * Every entry above that works on the grid lines takes mantis_image.K and
+ * mantis_image.D as exact. This call estimates them: from N views of one rig
+ * it runs a joint Gauss-Newton over the N base poses and the eight intrinsics
+ * (fx, fy, cx, cy, k1..k4) of the cameras named in `free_cams`, on the grid
+ * lines, and returns all of them with a covariance per free camera. All
+ * addition: no other entry point, struct, kernel result or draw changes,
+ * MANTIS_ABI_VERSION stays 5 (find the entries by name, check the sizes with
+ * mantis_icalib_sizes). The caller's mantis_images are never written; the
+ * context's prior, cv::RNG state and robust setting are neither read nor
+ * changed. The extrinsics are held at cams[c].T_base_cam: a caller who needs
+ * both alternates this call with mantis_calibrate_extrinsics.
+ *
+ * Unknowns. T_r = T_w_b of view r < N, and theta_c = (fx, fy, cx, cy, k1, k2,
+ * k3, k4) of every camera c named in free_cams. There is no gauge freedom (the
+ * map fixes the world, the extrinsics are held): free_cams may name every
+ * camera and C = 1 is legal. The start of theta_c is view 0's cams[c].K
+ * (rounded to float, as every other entry does) and cams[c].D (as given);
+ * every view's K and D of camera c must equal view 0's byte for byte. From
+ * then on theta lives in FP64 in the call's device state. A result fed back
+ * through mantis_image.K is rounded to float there: 6e-8 relative, harmless.
+ *
+ * Which parameters are free. param_mask bit i frees parameter i (in the order
+ * above, 0xFF = all) of every free camera. A held parameter's J_int column is
+ * zero in every row, its diagonal entry of B_f is set to exactly 1 after
+ * lambda is added, and its update is skipped: the value comes back bit for bit.
+ *
+ * One observation of (view r, camera c, candidate i) is exactly steps 1-8 of
+ * the line refinement (same candidates, window, codes, Sw, Skw, J_pose), with
+ * Cam = the current theta_c and the sample step s = 1 / fx of the current FP64
+ * estimate; r = -((double)Skw / (double)Sw) s. The slot's row has 15 entries
+ * [J_pose (6) | J_int (8) | r]; a rejected slot is fifteen zeros, a held
+ * camera has eight zeros for J_int. Slot index = c n_cand + candidate inside a
+ * view, no compaction.
+ *
+ * J_int belongs to the relative perturbation eps (8): fx <- fx (1 + eps0),
+ * fy <- fy (1 + eps1), cx <- cx + fx eps2, cy <- cy + fy eps3 (fx, fy before
+ * the update), k_i <- k_i + eps_(3+i). At m = m0 = (x, y) (step 1), rho = |m|,
+ * t = atan rho, t_d = t + k1 t^3 + k2 t^5 + k3 t^7 + k4 t^9,
+ * t_d' = 1 + 3 k1 t^2 + 5 k2 t^4 + 7 k3 t^6 + 9 k4 t^8, c = t_d / rho,
+ * c' = (t_d' / (1 + rho^2) - c) / rho, G = c I + (c' / rho) m m^T (the
+ * derivative of the normalized distortion), Q (2 x 8) with the columns
+ * (c x, 0), (0, c y), (1, 0), (0, 1), m t^3 / rho, m t^5 / rho, m t^7 / rho,
+ * m t^9 / rho: J_int = nh^T G^-1 Q, G inverted in closed form. For rho <= 1e-8
+ * (distort's own branch) G = I, c = 1 and the k columns are zero. (The line
+ * was seen at a fixed pixel P = dist(m_obs) and r = nh . (m0 - m_obs), so
+ * dr/dtheta = nh^T (d dist / d m)^-1 d dist / d theta.)
+ *
+ * A pass's accumulators. Per (view, camera): acc120 = the upper triangle, row
+ * by row, of M^T M for M = [J_pose | J_int | r] (blocks PP, PI, Pr, II, Ir,
+ * rr), and the count of code-0 rows. n_obs, n_obs_cam and rms as in the
+ * extrinsic calibration (integer sums; rr summed in (view, camera) order).
+ *
+ * The end of pass k < I is the extrinsic calibration's steps 1-8 with 8 in
+ * place of 6 for the camera blocks: the two starved gates (min_obs per view,
+ * min_obs_cam per free camera over the views; STARVED = 1), A_r = sum_c PP_rc
+ * + lambda I and its 6 x 6 Cholesky (SINGULAR = 2), Y_r = A_r^-1 [E_r | a_r]
+ * with E_r the PI blocks of the free cameras in ascending order (6 x 8 F),
+ * B_f = sum_r II_rf + lambda I (held parameters: see above), b_f = sum_r
+ * Ir_rf, S = B - sum_r E_r^T Y_r^E, s = -b + sum_r E_r^T Y_r^a (view order; S
+ * is at most 64 x 64), the left-looking Cholesky of S's lower triangle
+ * (SINGULAR), eps = S^-1 s, delta_r = -(Y_r^a + Y_r^E eps), T_r <- T_r
+ * D(delta_r), theta_c updated as above. If an updated fx or fy is not finite
+ * or <= 0, or any updated parameter is not finite: DIVERGED (3); the call
+ * stops and keeps the poses and parameters from before that step. I
+ * iterations are I + 1 observation passes; the last solves nothing. I = 0
+ * returns every pose bit for bit, every K as the float-rounded input and D as
+ * given. A stop ends the whole call (iterations_run = the steps taken;
+ * entries past it are 0).
+ *
+ * Gate and covariance (host). dof = n_obs - 6 N - P, P the number of free
+ * parameters over the free cameras. calibrated = status OK && no starved gate
+ * on the final pass && (max_rms <= 0 || final rms <= max_rms) && dof > 0 && S
+ * of the final pass with lambda = 0 positive definite. covariance[c] (8 x 8,
+ * row-major) = (r^T r / dof) (S^-1)_cc scaled by diag(fx, fy, fx, fy, 1, 1, 1,
+ * 1) on both sides: px^2 for K, dimensionless for D. Zeros in a held
+ * parameter's row and column, for a held camera and when calibrated = 0.
+ * rms_cam[c] of the final pass as in the extrinsic calibration. */
+typedef struct mantis_icalib_params {
+  int32_t struct_size;   /* sizeof(mantis_icalib_params) */
+  int32_t free_cams;     /* bit c: camera c's intrinsics are unknown */
+  int32_t param_mask;    /* bit i: parameter i (fx, fy, cx, cy, k1..k4) is free; 1..0xFF */
+  int32_t min_obs_cam;   /* >= 8 */
+} mantis_icalib_params;
+/* free_cams 0 (the caller names them) / param_mask 0xFF / min_obs_cam 60 */
+void mantis_default_icalib_params(mantis_icalib_params* p);
+
+typedef struct mantis_icalib_result {
+  int32_t status, calibrated, iterations_run, n_cand; /* status: 0 OK, 1 STARVED, 2 SINGULAR, 3 DIVERGED */
+  int32_t n_rigs, n_cams, free_cams, param_mask;
+  double K[8][4];             /* fx, fy, cx, cy; the (float-rounded) input for held cameras; zeros past n_cams */
+  double D[8][4];             /* k1..k4 */
+  int32_t n_obs[11];          /* per pass */
+  int32_t pad;
+  int32_t n_obs_cam[11][8];
+  double rms[11];
+  double rms_cam[8];          /* of the final pass */
+  double delta_cam[10][8][8]; /* eps per pass and camera; zeros for held cameras and held parameters */
+  double covariance[8][64];
+} mantis_icalib_result;
+/* sizeof(mantis_icalib_params), sizeof(mantis_icalib_result) (host only) */
+void mantis_icalib_sizes(int32_t* params_bytes, int32_t* result_bytes);
+
+/* n_rigs views of one rig of cams_per_rig cameras, laid out and started as in
+ * mantis_calibrate_extrinsics; the window, gates, lambda, pitch, iterations
+ * and `record` come from p. Limits and errors are those of
+ * mantis_calibrate_extrinsics (MANTIS_ERR_ARG, nothing launched,
+ * mantis_last_error names the field), except: cams_per_rig >= 1; free_cams
+ * may name every camera, but not none and no bit at or above cams_per_rig;
+ * param_mask in 1..0xFF; min_obs_cam >= 8; a K or D that is not finite, or
+ * fx or fy <= 0; a view whose K, D or T_base_cam differs from view 0's in any
+ * byte. Device work: 3 (I + 1) launches on the context stream (k_icalib_obs,
+ * k_icalib_rig, k_icalib_solve per pass), then the copies of the results. */
+mantis_status mantis_calibrate_intrinsics(void* ctx, const mantis_image* cams, int32_t n_rigs, int32_t cams_per_rig,
+                                          const double* T_w_b_in, const mantis_refine_params* p,
+                                          const mantis_icalib_params* ip, double* T_w_b_out, mantis_icalib_result* out);
+/* Record of view `rig`, pass 0 .. iterations_run, of the last intrinsic
+ * calibration made with p->record = 1; each pointer nullable: T_w_b (16) and
+ * KD (C x 8: fx, fy, cx, cy, k1..k4) the pass observed at; per slot (C x
+ * n_cand) codes, Sw, Skw and rows (15 doubles each); acc120 (C x 120) of the
+ * view. MANTIS_ERR_STATE: no such record. MANTIS_ERR_ARG: rig or pass out of
+ * range. */
+mantis_status mantis_get_icalib_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, double* KD, int32_t* codes,
+                                       int32_t* Sw, int32_t* Skw, double* rows, double* acc120);
+
 #ifdef __cplusplus
 }
 #endif

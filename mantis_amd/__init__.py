@@ -146,6 +146,19 @@ class MantisCalibResult(C.Structure):
                 ("delta_cam", ((C.c_double * 6) * 8) * 10), ("covariance", (C.c_double * 36) * 8)]
 
 
+class MantisIcalibParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("free_cams", C.c_int32), ("param_mask", C.c_int32),
+                ("min_obs_cam", C.c_int32)]
+
+
+class MantisIcalibResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("calibrated", C.c_int32), ("iterations_run", C.c_int32), ("n_cand", C.c_int32),
+                ("n_rigs", C.c_int32), ("n_cams", C.c_int32), ("free_cams", C.c_int32), ("param_mask", C.c_int32),
+                ("K", (C.c_double * 4) * 8), ("D", (C.c_double * 4) * 8), ("n_obs", C.c_int32 * 11), ("pad", C.c_int32),
+                ("n_obs_cam", (C.c_int32 * 8) * 11), ("rms", C.c_double * 11), ("rms_cam", C.c_double * 8),
+                ("delta_cam", ((C.c_double * 8) * 8) * 10), ("covariance", (C.c_double * 64) * 8)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -288,6 +301,12 @@ _SIGS = {
                                               C.POINTER(MantisRefineParams), C.POINTER(MantisCalibParams), C.c_void_p,
                                               C.POINTER(MantisCalibResult)]),
     "mantis_get_calib_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "mantis_default_icalib_params": (None, [C.POINTER(MantisIcalibParams)]),
+    "mantis_icalib_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_calibrate_intrinsics": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32, C.c_void_p,
+                                              C.POINTER(MantisRefineParams), C.POINTER(MantisIcalibParams), C.c_void_p,
+                                              C.POINTER(MantisIcalibResult)]),
+    "mantis_get_icalib_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "mantis_mcl_refine_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mantis_mcl_refine_modes": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32,
                                           C.POINTER(MantisRefineParams), C.c_int32, C.POINTER(MantisMclRefined)]),
@@ -740,6 +759,66 @@ class Mantis:
                                                 Sw.ctypes.data, Skw.ctypes.data, rows.ctypes.data, acc.ctypes.data),
                   "get_calib_record")
         return T, E, codes, Sw, Skw, rows, acc
+
+    # intrinsic calibration (mantis_calibrate_intrinsics, include/mantis.h) ----
+    def icalib_params(self, free_cams, **params):
+        """mantis_default_icalib_params with `free_cams` (a bit mask or an iterable of camera indices)."""
+        p = MantisIcalibParams()
+        lib().mantis_default_icalib_params(C.byref(p))
+        if not isinstance(free_cams, int):
+            free_cams = sum(1 << int(c) for c in free_cams)
+        p.free_cams = free_cams
+        for k, v in params.items():
+            if k not in ("param_mask", "min_obs_cam"):
+                raise TypeError(f"icalib: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def calibrate_intrinsics(self, images, views, T_in, free_cams, param_mask=None, min_obs_cam=None, **refine_params):
+        """mantis_calibrate_intrinsics: `views` views of one rig (images
+        view-major, every view with the rig's nominal K, D and T_base_cam) from
+        the base poses T_in (views x 4 x 4); `free_cams` names the cameras
+        whose intrinsics are unknown, `param_mask` which of (fx, fy, cx, cy,
+        k1..k4) are. Returns (T_w_b [views, 4, 4], MantisIcalibResult); a K
+        fed back through make_image is rounded to float there."""
+        n = len(images)
+        assert views > 0 and n % views == 0
+        cams = (MantisImage * n)(*images)
+        T = np.ascontiguousarray(T_in, np.float64).reshape(-1)
+        assert T.size == 16 * views
+        p = self.refine_params(**refine_params)
+        kw = {k: v for k, v in (("param_mask", param_mask), ("min_obs_cam", min_obs_cam)) if v is not None}
+        ip = self.icalib_params(free_cams, **kw)
+        T_out = np.zeros((views, 4, 4))
+        out = MantisIcalibResult()
+        self._chk(lib().mantis_calibrate_intrinsics(self.h, cams, views, n // views, T.ctypes.data, C.byref(p),
+                                                    C.byref(ip), T_out.ctypes.data, C.byref(out)),
+                  "calibrate_intrinsics")
+        self._icalib_shape = (n // views, out.n_cand)
+        return T_out, out
+
+    def icalib_record(self, rig, pass_):
+        """Pass `pass_` (0 .. iterations_run) of view `rig` of the last
+        intrinsic calibration made with record=1 (mantis_get_icalib_record):
+        (T_w_b [4, 4], KD [C, 8] = fx, fy, cx, cy, k1..k4, codes, Sw, Skw
+        [slots] int32, rows [slots, 15], acc120 [C, 120]); slot = camera x
+        n_cand + candidate."""
+        shape = getattr(self, "_icalib_shape", None)
+        if shape is None:
+            raise MantisError("icalib_record: no intrinsic calibration on this context")
+        Cn, nc = shape
+        ns = Cn * nc
+        T = np.zeros((4, 4))
+        KD = np.zeros((Cn, 8))
+        codes = np.zeros(ns, np.int32)
+        Sw = np.zeros(ns, np.int32)
+        Skw = np.zeros(ns, np.int32)
+        rows = np.zeros((ns, 15))
+        acc = np.zeros((Cn, 120))
+        self._chk(lib().mantis_get_icalib_record(self.h, rig, pass_, T.ctypes.data, KD.ctypes.data, codes.ctypes.data,
+                                                 Sw.ctypes.data, Skw.ctypes.data, rows.ctypes.data, acc.ctypes.data),
+                  "get_icalib_record")
+        return T, KD, codes, Sw, Skw, rows, acc
 
     # Monte Carlo localization (mantis_mcl_*, include/mantis.h) ---------------
     def mcl_params(self, **params):

@@ -371,6 +371,18 @@ struct Ctx {
     size_t slot_cap = 0, racc_cap = 0;
     int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
   } cb;
+  // intrinsic calibration (icalib_impl.hip): as `cb`, with the passes' intrinsics in place of the extrinsics
+  // (mantis_get_icalib_record)
+  struct Icalib {
+    void *d_state = nullptr, *h_state = nullptr;  // IcalibState; h: pinned, with the poses, accumulators and counts behind it
+    double *d_T = nullptr, *d_acc = nullptr, *d_Y = nullptr, *d_Wt = nullptr;
+    int32_t *d_cnt = nullptr, *d_pd = nullptr;
+    double *d_recT = nullptr, *d_recKD = nullptr, *d_recAcc = nullptr;  // [pass][view][16], [pass][C][8], [pass][view][C][120]
+    void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
+    int view_cap = 0;
+    size_t slot_cap = 0, racc_cap = 0;
+    int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
+  } ib;
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1421,6 +1433,11 @@ mantis_status mantis_destroy(void* ctx) {
   for (void* p : cptrs)
     if (p) (void)hipFree(p);
   if (c->cb.h_state) (void)hipHostFree(c->cb.h_state);
+  void* iptrs[] = {c->ib.d_state, c->ib.d_T, c->ib.d_acc, c->ib.d_Y, c->ib.d_Wt, c->ib.d_cnt, c->ib.d_pd,
+                   c->ib.d_recT, c->ib.d_recKD, c->ib.d_recAcc, c->ib.d_slots};
+  for (void* p : iptrs)
+    if (p) (void)hipFree(p);
+  if (c->ib.h_state) (void)hipHostFree(c->ib.h_state);
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
                    c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes, c->mcl.h_moved};
@@ -1471,6 +1488,7 @@ mantis_status mantis_set_map(void* ctx, const double* white, int32_t nw, const d
   c->rf.pitch = 0;  // the line flags of the previous map go (refine_impl.hip)
   c->rf.rigs = 0;
   c->cb.rigs = 0;
+  c->ib.rigs = 0;
   return MANTIS_OK;
 }
 
@@ -2277,5 +2295,6 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "mcl_color_impl.hip"
 #include "refine_impl.hip"
 #include "calib_impl.hip"
+#include "icalib_impl.hip"
 #include "mcl_refine_impl.hip"
 #include "ros_wire.h"
