@@ -220,6 +220,7 @@ struct Ctx {
   // pinned host
   float* h_gauss = nullptr;
   uint64_t* h_states = nullptr;
+  std::vector<uint64_t> frame_rng;  // cv::RNG state after each frame of the last process call (FrameDebug); empty after a failed one
   mantis_cam_result* h_res = nullptr;
   FrameState* h_st = nullptr;
   int32_t* h_gtotal = nullptr;
@@ -998,6 +999,7 @@ Ctx::CallGraph* call_graph(Ctx* c, int n, int W, int H, const Shard* sh) {
 mantis_status process_frames(Ctx* c, const mantis_image* cams, int n, const Shard* sh = nullptr) {
   if (!c->d_lm) { c->err = "map not set (mantis_set_map)"; return MANTIS_ERR_STATE; }
   if (n <= 0 || n > c->F) { c->err = "frame count exceeds max_cams"; return MANTIS_ERR_ARG; }
+  c->frame_rng.clear();  // the records are rewritten from here on: no state of an earlier call completes them
   const int ng = sh ? sh->n_global : n;
   // the gaussian offsets are int32 on the device (FrameState::gauss_offset)
   if ((int64_t)c->cfg.particles * c->cfg.iterations * 6 * ng > INT32_MAX) {
@@ -1085,6 +1087,22 @@ mantis_status process_frames(Ctx* c, const mantis_image* cams, int n, const Shar
     }
   }
   if (used * per != *c->h_gtotal) { c->err = "internal: gaussian stream accounting mismatch"; return MANTIS_ERR_DEVICE; }
+  // the reference's RNG state after each frame, in the order the sequential
+  // reference processes them: the stream position after the frames up to and
+  // including this one that reached the particle filter (sharded: up to its
+  // global index). The frame record's rng_state_after (mantis_get_frame_debug).
+  c->frame_rng.resize(n);
+  if (sh) {
+    std::vector<int> upto(ng + 1, 0);
+    for (int f = 0; f < ng; f++) upto[f + 1] = upto[f] + (c->h_sh_flags[f] ? 1 : 0);
+    for (int f = 0; f < n; f++) c->frame_rng[f] = c->h_states[upto[sh->gidx[f] + 1]];
+  } else {
+    int k = 0;
+    for (int f = 0; f < n; f++) {
+      if (c->h_st[f].reaches_pf) k++;
+      c->frame_rng[f] = c->h_states[k];
+    }
+  }
   c->rng_state = c->h_states[used];
   return MANTIS_OK;
 }
@@ -1927,6 +1945,7 @@ mantis_status mantis_get_frame_debug(void* ctx, int32_t frame, void* out, size_t
   }
   HIP_OK(hipMemcpy(out, c->d_dbg + frame, sizeof(FrameDebug), hipMemcpyDeviceToHost));
   // the host-side RNG bookkeeping completes the record
+  if ((size_t)frame < c->frame_rng.size()) ((FrameDebug*)out)->rng_state_after = c->frame_rng[frame];
   return MANTIS_OK;
 }
 size_t mantis_frame_debug_size(void) { return sizeof(FrameDebug); }
@@ -2042,6 +2061,7 @@ mantis_status mantis_detect_quads(void* ctx, const mantis_image* img, int32_t* c
   int W, H;
   mantis_status st = stage_frames(c, img, 1, W, H);
   if (st != MANTIS_OK) return st;
+  c->frame_rng.clear();  // run_contours rewrites frame 0's record
   if ((st = run_image_stages(c, 1, W, H)) != MANTIS_OK) return st;
   if ((st = run_contours(c, 1, W, H)) != MANTIS_OK) return st;
   HIP_OK(hipMemcpyAsync(c->h_st, c->d_st, sizeof(FrameState), hipMemcpyDeviceToHost, c->s));

@@ -137,6 +137,9 @@ def test_config4_8cam_1080p_rig_and_sharded_one_rank(landmark_map):
         assert bytes(a) == bytes(b)
     for a, b in zip(cb, cs):
         assert bytes(a) == bytes(b)
+    for i in range(n_rigs * n_cams):  # the frame record's RNG state: the reference's after that frame
+        assert mb.frame_debug(i).rng_state_after == states[i], i
+        assert ms.frame_debug(i).rng_state_after == states[i], i
     for r in range(n_rigs):
         ia, oa = mb.rig_gn(r)
         ib, ob = ms.rig_gn(r)
@@ -152,6 +155,8 @@ def test_config4_8cam_1080p_rig_and_sharded_one_rank(landmark_map):
     bad[3].step_bytes = 3 * W - 3
     with pytest.raises(M.MantisError, match="step"):
         ms.process_sharded(bad, n_rigs, list(range(n_cams)), n_cams)
+    # a failed call leaves no RNG state of the call before it in the frame records
+    assert ms.frame_debug(0).rng_state_after == 0
     ms.rng_state = 1
     rs2, _ = ms.process_sharded(imgs, n_rigs, list(range(n_cams)), n_cams)
     for a, b in zip(rb, rs2):
