@@ -1087,7 +1087,8 @@ mantis_status mantis_get_calib_record(void* ctx, int32_t rig, int32_t pass, doub
  * mantis_icalib_sizes). The caller's mantis_images are never written; the
  * context's prior, cv::RNG state and robust setting are neither read nor
  * changed. The extrinsics are held at cams[c].T_base_cam: a caller who needs
- * both alternates this call with mantis_calibrate_extrinsics.
+ * both calls mantis_calibrate_rig (below), which solves for them together
+ * (alternating this call with mantis_calibrate_extrinsics does not converge).
  *
  * Unknowns. T_r = T_w_b of view r < N, and theta_c = (fx, fy, cx, cy, k1, k2,
  * k3, k4) of every camera c named in free_cams. There is no gauge freedom (the
@@ -1200,6 +1201,124 @@ mantis_status mantis_calibrate_intrinsics(void* ctx, const mantis_image* cams, i
  * range. */
 mantis_status mantis_get_icalib_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, double* KD, int32_t* codes,
                                        int32_t* Sw, int32_t* Skw, double* rows, double* acc120);
+
+/* ---- Rig calibration: poses + extrinsics + intrinsics in one solve ----
+ * mantis_calibrate_extrinsics takes every K and D as exact,
+ * mantis_calibrate_intrinsics every T_base_cam. On a rig where neither is
+ * exact each of them absorbs the other's error into its own unknowns, and
+ * alternating them does not converge to the rig (DESIGN 4j has the figures).
+ * This call estimates all of it at once: from N views of one rig it runs a
+ * joint Gauss-Newton over the N base poses, the extrinsics of the cameras
+ * named in `free_ext` and the eight intrinsics of the cameras named in
+ * `free_int`, on the grid lines. All addition: no other entry point, struct,
+ * kernel result or draw changes, MANTIS_ABI_VERSION stays 5 (find the entries
+ * by name, check the sizes with mantis_rcalib_sizes). The caller's
+ * mantis_images are never written; the context's prior, cv::RNG state and
+ * robust setting are neither read nor changed.
+ *
+ * Unknowns. T_r = T_w_b of view r < N (N <= 256); E_c = T_base_cam of every
+ * camera in free_ext; theta_c = (fx, fy, cx, cy, k1..k4) of every camera in
+ * free_int. Both masks must name a camera. Gauge as in the extrinsic
+ * calibration: free_ext must leave at least one camera held (so C >= 2);
+ * free_int may name every camera. param_mask has the intrinsic calibration's
+ * meaning, the exact 1 on a held parameter's diagonal included. Starts: view
+ * 0's T_base_cam, K rounded to float, D as given; every view's T_base_cam, K
+ * and D must equal view 0's byte for byte.
+ *
+ * One observation is the intrinsic calibration's, taken at the current theta_c
+ * and at R_cb / t_cb = inverse(current E_c), with the sample step s = 1 / fx
+ * of the current estimate. The slot's row has 21 entries
+ * [J_pose (6) | J_ext (6) | J_int (8) | r]: J_ext is the extrinsic
+ * calibration's [-g | g [p]x] from the same geometry, J_int the intrinsic
+ * calibration's. A camera held in a mask has zeros in that block; a rejected
+ * slot is 21 zeros. With free_int's bit clear (and a float-representable K)
+ * columns 0-11 and 20, the codes and the sums equal the extrinsic
+ * calibration's slot bit for bit; with free_ext's bit clear columns 0-5 and
+ * 12-20 equal the intrinsic calibration's.
+ *
+ * A pass's accumulators. Per (view, camera): acc231 = the upper triangle, row
+ * by row, of M^T M for M = [J_pose | J_ext | J_int | r] (blocks PP, PE, PI,
+ * Pr, EE, EI, Er, II, Ir, rr), and the count of code-0 rows. n_obs, n_obs_cam
+ * and rms as in the other two calibrations.
+ *
+ * The end of pass k < I is the extrinsic calibration's steps 1-8. The reduced
+ * unknowns are the extrinsic blocks of free_ext (ascending cameras, 6 each),
+ * then the intrinsic blocks of free_int (ascending, 8 each): nS = 6 Fe + 8 Fi
+ * <= 106. Both starved gates apply, min_obs_cam to a camera free in either
+ * mask (STARVED = 1). A_r = sum_c PP_rc + lambda I and its 6 x 6 Cholesky
+ * (SINGULAR = 2); [E_r | a_r] (6 x (nS + 1)) = the PE and PI blocks of the
+ * free cameras in the order above and sum_c Pr_rc; Y_r = A_r^-1 [E_r | a_r].
+ * B is block diagonal per camera: EE (+ lambda I) and II (+ lambda I; a held
+ * parameter's diagonal entry exactly 1) summed over the views, and for a
+ * camera free in both masks the off-diagonal block sum_r EI. b = the Er and
+ * Ir sums. S = B - sum_r E_r^T Y_r^E, s = -b + sum_r E_r^T Y_r^a, every sum in
+ * view order; the left-looking Cholesky of S's lower triangle (SINGULAR);
+ * eps = S^-1 s; delta_r = -(Y_r^a + Y_r^E eps); T_r <- T_r D(delta_r), E_c <-
+ * E_c D(eps_c), theta_c updated as in the intrinsic calibration. If an updated
+ * fx or fy is not finite or <= 0, or any updated parameter is not finite:
+ * DIVERGED (3); the call stops and keeps the poses, extrinsics and parameters
+ * from before that step. I = 0 returns every pose and extrinsic bit for bit,
+ * K as the float-rounded input and D as given.
+ *
+ * Gate and covariance (host). dof = n_obs - 6 N - 6 Fe - P, P the number of
+ * free parameters over the cameras of free_int. calibrated = status OK && no
+ * starved gate on the final pass && (max_rms <= 0 || final rms <= max_rms) &&
+ * dof > 0 && S of the final pass with lambda = 0 positive definite.
+ * cov_ext[c] (6 x 6) and cov_int[c] (8 x 8, scaled by diag(fx, fy, fx, fy, 1,
+ * 1, 1, 1) on both sides) are the diagonal blocks of (r^T r / dof) S^-1.
+ * Zeros where held and when calibrated = 0. */
+typedef struct mantis_rcalib_params {
+  int32_t struct_size;   /* sizeof(mantis_rcalib_params) */
+  int32_t free_ext;      /* bit c: camera c's extrinsic is unknown; at least one camera held */
+  int32_t free_int;      /* bit c: camera c's intrinsics are unknown */
+  int32_t param_mask;    /* bit i: parameter i (fx, fy, cx, cy, k1..k4) is free; 1..0xFF */
+  int32_t min_obs_cam;   /* >= 14 */
+  int32_t pad;
+} mantis_rcalib_params;
+/* free_ext 0 / free_int 0 (the caller names them) / param_mask 0xFF / min_obs_cam 60 */
+void mantis_default_rcalib_params(mantis_rcalib_params* p);
+
+typedef struct mantis_rcalib_result {
+  int32_t status, calibrated, iterations_run, n_cand; /* status: 0 OK, 1 STARVED, 2 SINGULAR, 3 DIVERGED */
+  int32_t n_rigs, n_cams, free_ext, free_int;
+  int32_t param_mask, pad;
+  double T_base_cam[8][16];   /* row-major; the input for cameras held in free_ext; zeros past n_cams */
+  double K[8][4];             /* fx, fy, cx, cy; the (float-rounded) input for cameras held in free_int */
+  double D[8][4];             /* k1..k4 */
+  int32_t n_obs[11];          /* per pass */
+  int32_t pad2;
+  int32_t n_obs_cam[11][8];
+  double rms[11];
+  double rms_cam[8];          /* of the final pass */
+  double delta_ext[10][8][6]; /* eps per pass and camera; zeros where held */
+  double delta_int[10][8][8];
+  double cov_ext[8][36];
+  double cov_int[8][64];
+} mantis_rcalib_result;
+/* sizeof(mantis_rcalib_params), sizeof(mantis_rcalib_result) (host only) */
+void mantis_rcalib_sizes(int32_t* params_bytes, int32_t* result_bytes);
+
+/* n_rigs views of one rig of cams_per_rig cameras, laid out and started as in
+ * the other two calibrations; the window, gates, lambda, pitch, iterations and
+ * `record` come from p. Errors (MANTIS_ERR_ARG, nothing launched,
+ * mantis_last_error names the field): those of mantis_calibrate_extrinsics
+ * and mantis_calibrate_intrinsics together, with free_ext and free_int in
+ * place of free_cams: either mask empty or with a bit at or above
+ * cams_per_rig, free_ext naming every camera, min_obs_cam < 14.
+ * MANTIS_ERR_STATE: the device refused the solve kernel's LDS. Device work:
+ * 3 (I + 1) launches on the context stream (k_rcalib_obs, k_rcalib_rig,
+ * k_rcalib_solve per pass), then the copies of the results. */
+mantis_status mantis_calibrate_rig(void* ctx, const mantis_image* cams, int32_t n_rigs, int32_t cams_per_rig,
+                                   const double* T_w_b_in, const mantis_refine_params* p,
+                                   const mantis_rcalib_params* rp, double* T_w_b_out, mantis_rcalib_result* out);
+/* Record of view `rig`, pass 0 .. iterations_run, of the last rig calibration
+ * made with p->record = 1; each pointer nullable: T_w_b (16), T_base_cam (C x
+ * 16) and KD (C x 8) the pass observed at; per slot (C x n_cand) codes, Sw,
+ * Skw and rows (21 doubles each); acc231 (C x 231) of the view.
+ * MANTIS_ERR_STATE: no such record. MANTIS_ERR_ARG: rig or pass out of range. */
+mantis_status mantis_get_rcalib_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, double* T_base_cam,
+                                       double* KD, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows,
+                                       double* acc231);
 
 #ifdef __cplusplus
 }

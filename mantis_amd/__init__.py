@@ -159,6 +159,22 @@ class MantisIcalibResult(C.Structure):
                 ("delta_cam", ((C.c_double * 8) * 8) * 10), ("covariance", (C.c_double * 64) * 8)]
 
 
+class MantisRcalibParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("free_ext", C.c_int32), ("free_int", C.c_int32),
+                ("param_mask", C.c_int32), ("min_obs_cam", C.c_int32), ("pad", C.c_int32)]
+
+
+class MantisRcalibResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("calibrated", C.c_int32), ("iterations_run", C.c_int32), ("n_cand", C.c_int32),
+                ("n_rigs", C.c_int32), ("n_cams", C.c_int32), ("free_ext", C.c_int32), ("free_int", C.c_int32),
+                ("param_mask", C.c_int32), ("pad", C.c_int32),
+                ("T_base_cam", (C.c_double * 16) * 8), ("K", (C.c_double * 4) * 8), ("D", (C.c_double * 4) * 8),
+                ("n_obs", C.c_int32 * 11), ("pad2", C.c_int32), ("n_obs_cam", (C.c_int32 * 8) * 11),
+                ("rms", C.c_double * 11), ("rms_cam", C.c_double * 8),
+                ("delta_ext", ((C.c_double * 6) * 8) * 10), ("delta_int", ((C.c_double * 8) * 8) * 10),
+                ("cov_ext", (C.c_double * 36) * 8), ("cov_int", (C.c_double * 64) * 8)]
+
+
 class SynthCamC(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("k", C.c_double * 4), ("R_wc", C.c_double * 9), ("pos", C.c_double * 3),
@@ -307,6 +323,12 @@ _SIGS = {
                                               C.POINTER(MantisRefineParams), C.POINTER(MantisIcalibParams), C.c_void_p,
                                               C.POINTER(MantisIcalibResult)]),
     "mantis_get_icalib_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "mantis_default_rcalib_params": (None, [C.POINTER(MantisRcalibParams)]),
+    "mantis_rcalib_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_calibrate_rig": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32, C.c_void_p,
+                                       C.POINTER(MantisRefineParams), C.POINTER(MantisRcalibParams), C.c_void_p,
+                                       C.POINTER(MantisRcalibResult)]),
+    "mantis_get_rcalib_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
     "mantis_mcl_refine_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mantis_mcl_refine_modes": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32,
                                           C.POINTER(MantisRefineParams), C.c_int32, C.POINTER(MantisMclRefined)]),
@@ -819,6 +841,69 @@ class Mantis:
                                                  Sw.ctypes.data, Skw.ctypes.data, rows.ctypes.data, acc.ctypes.data),
                   "get_icalib_record")
         return T, KD, codes, Sw, Skw, rows, acc
+
+    # rig calibration (mantis_calibrate_rig, include/mantis.h) ----------------
+    def rcalib_params(self, free_ext, free_int, **params):
+        """mantis_default_rcalib_params with `free_ext` and `free_int` (bit masks or iterables of camera indices)."""
+        p = MantisRcalibParams()
+        lib().mantis_default_rcalib_params(C.byref(p))
+        mask = lambda m: m if isinstance(m, int) else sum(1 << int(c) for c in m)
+        p.free_ext = mask(free_ext)
+        p.free_int = mask(free_int)
+        for k, v in params.items():
+            if k not in ("param_mask", "min_obs_cam"):
+                raise TypeError(f"rcalib: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def calibrate_rig(self, images, views, T_in, free_ext, free_int, param_mask=None, min_obs_cam=None,
+                      **refine_params):
+        """mantis_calibrate_rig: `views` views of one rig (images view-major,
+        every view with the rig's nominal K, D and T_base_cam) from the base
+        poses T_in (views x 4 x 4); `free_ext` names the cameras whose
+        extrinsics are unknown (one at least stays held), `free_int` those
+        whose intrinsics are, `param_mask` which of (fx, fy, cx, cy, k1..k4).
+        Returns (T_w_b [views, 4, 4], MantisRcalibResult)."""
+        n = len(images)
+        assert views > 0 and n % views == 0
+        cams = (MantisImage * n)(*images)
+        T = np.ascontiguousarray(T_in, np.float64).reshape(-1)
+        assert T.size == 16 * views
+        p = self.refine_params(**refine_params)
+        kw = {k: v for k, v in (("param_mask", param_mask), ("min_obs_cam", min_obs_cam)) if v is not None}
+        rp = self.rcalib_params(free_ext, free_int, **kw)
+        T_out = np.zeros((views, 4, 4))
+        out = MantisRcalibResult()
+        self._chk(lib().mantis_calibrate_rig(self.h, cams, views, n // views, T.ctypes.data, C.byref(p), C.byref(rp),
+                                             T_out.ctypes.data, C.byref(out)),
+                  "calibrate_rig")
+        self._rcalib_shape = (n // views, out.n_cand)
+        return T_out, out
+
+    def rcalib_record(self, rig, pass_):
+        """Pass `pass_` (0 .. iterations_run) of view `rig` of the last rig
+        calibration made with record=1 (mantis_get_rcalib_record): (T_w_b
+        [4, 4], T_base_cam [C, 4, 4], KD [C, 8] = fx, fy, cx, cy, k1..k4,
+        codes, Sw, Skw [slots] int32, rows [slots, 21], acc231 [C, 231]);
+        slot = camera x n_cand + candidate."""
+        shape = getattr(self, "_rcalib_shape", None)
+        if shape is None:
+            raise MantisError("rcalib_record: no rig calibration on this context")
+        Cn, nc = shape
+        ns = Cn * nc
+        T = np.zeros((4, 4))
+        E = np.zeros((Cn, 4, 4))
+        KD = np.zeros((Cn, 8))
+        codes = np.zeros(ns, np.int32)
+        Sw = np.zeros(ns, np.int32)
+        Skw = np.zeros(ns, np.int32)
+        rows = np.zeros((ns, 21))
+        acc = np.zeros((Cn, 231))
+        self._chk(lib().mantis_get_rcalib_record(self.h, rig, pass_, T.ctypes.data, E.ctypes.data, KD.ctypes.data,
+                                                 codes.ctypes.data, Sw.ctypes.data, Skw.ctypes.data, rows.ctypes.data,
+                                                 acc.ctypes.data),
+                  "get_rcalib_record")
+        return T, E, KD, codes, Sw, Skw, rows, acc
 
     # Monte Carlo localization (mantis_mcl_*, include/mantis.h) ---------------
     def mcl_params(self, **params):

@@ -384,6 +384,20 @@ struct Ctx {
     size_t slot_cap = 0, racc_cap = 0;
     int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
   } ib;
+  // rig calibration (rcalib_impl.hip): as `cb` and `ib` together, with the passes' extrinsics and intrinsics
+  // (mantis_get_rcalib_record); lds_ok: k_rcalib_solve may take its dynamic LDS (asked once)
+  struct Rcalib {
+    void *d_state = nullptr, *h_state = nullptr;  // RcalibState; h: pinned, with the poses, accumulators and counts behind it
+    double *d_T = nullptr, *d_acc = nullptr, *d_Y = nullptr, *d_Wt = nullptr;
+    int32_t *d_cnt = nullptr, *d_pd = nullptr;
+    // [pass][view][16], [pass][C][16], [pass][C][8], [pass][view][C][231]
+    double *d_recT = nullptr, *d_recE = nullptr, *d_recKD = nullptr, *d_recAcc = nullptr;
+    void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
+    int view_cap = 0;
+    size_t slot_cap = 0, racc_cap = 0;
+    bool lds_asked = false, lds_ok = false;
+    int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
+  } rb;
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1456,6 +1470,11 @@ mantis_status mantis_destroy(void* ctx) {
   for (void* p : iptrs)
     if (p) (void)hipFree(p);
   if (c->ib.h_state) (void)hipHostFree(c->ib.h_state);
+  void* bptrs[] = {c->rb.d_state, c->rb.d_T, c->rb.d_acc, c->rb.d_Y, c->rb.d_Wt, c->rb.d_cnt, c->rb.d_pd,
+                   c->rb.d_recT, c->rb.d_recE, c->rb.d_recKD, c->rb.d_recAcc, c->rb.d_slots};
+  for (void* p : bptrs)
+    if (p) (void)hipFree(p);
+  if (c->rb.h_state) (void)hipHostFree(c->rb.h_state);
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
                    c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes, c->mcl.h_moved};
@@ -1507,6 +1526,7 @@ mantis_status mantis_set_map(void* ctx, const double* white, int32_t nw, const d
   c->rf.rigs = 0;
   c->cb.rigs = 0;
   c->ib.rigs = 0;
+  c->rb.rigs = 0;
   return MANTIS_OK;
 }
 
@@ -2316,5 +2336,6 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "refine_impl.hip"
 #include "calib_impl.hip"
 #include "icalib_impl.hip"
+#include "rcalib_impl.hip"
 #include "mcl_refine_impl.hip"
 #include "ros_wire.h"

@@ -15,6 +15,7 @@ static int g_jacobi_ff = 1;
 #include "mk_bits.h"
 #include "mk_calib.h"
 #include "mk_icalib.h"
+#include "mk_rcalib.h"
 #include "mk_contour.h"
 #include "mk_gn.h"
 #include "mk_math.h"
@@ -793,6 +794,77 @@ void hc_icalib_conclude(const double* acc120, const int32_t* cnt, int N, int C, 
 }
 int hc_sizeof_icalib_params(void) { return (int)sizeof(mantis_icalib_params); }
 int hc_sizeof_icalib_result(void) { return (int)sizeof(mantis_icalib_result); }
+
+// Rig calibration (mk_rcalib.h): the rules k_rcalib_obs / k_rcalib_rig / k_rcalib_solve run.
+// hc_icalib_obs with rows of 21 ([J_pose | J_ext | J_int | r]; J_ext zeros unless free_ext, J_int zeros
+// unless free_int, a zero for a parameter outside param_mask)
+int hc_rcalib_obs(const double* Twb, const double* Tbc, const double* KD, const uint8_t* bgr, int W, int H,
+                  const double* X, int nw, int nr, int ng, const uint8_t* flags, int R, int white_thresh, int min_weight,
+                  int free_ext, int free_int, int param_mask, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows,
+                  int32_t* tie) {
+  namespace rf = mk::refine;
+  const int n = nw + nr + ng;
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags, n, cand.data());
+  mk::GnCam gc;
+  rf::gncam_from(Tbc, gc);
+  const mk::Cam cm = mk::icalib::cam_of(KD, KD + 4);
+  double Rt[9], t[3];
+  rf::pose_parts(Twb, Rt, t);
+  const rf::Window win{R, white_thresh, min_weight, 0};
+  for (int k = 0; k < nc; k++) {
+    const int i = cand[k] & 0xffff, axis = cand[k] >> 16;
+    int tg[3], near = 0;
+    rf::target_bgr(i, nw, nr, tg);
+    mk::rcalib::Slot o;
+    mk::rcalib::observe(Rt, t, gc, cm, bgr, W, H, X + 3 * i, axis, tg, win, free_ext != 0, free_int != 0,
+                        (uint32_t)param_mask, o, &near);
+    codes[k] = o.code;
+    Sw[k] = o.Sw;
+    Skw[k] = o.Skw;
+    std::memcpy(rows + mk::rcalib::kRow * k, o.row, sizeof(o.row));
+    if (tie) tie[k] = near;
+  }
+  return nc;
+}
+// acc231 of n rows of 21 doubles, summed in row order
+void hc_rcalib_accumulate(const double* rows, int n, double* acc231) {
+  for (int e = 0; e < mk::rcalib::kAcc; e++) acc231[e] = 0.0;
+  for (int k = 0; k < n; k++) mk::rcalib::accumulate_row(rows + mk::rcalib::kRow * k, acc231);
+}
+// the end of a pass from given accumulators (N x C x 231) and counts (N x C): T (N x 16, in / out),
+// R->T_base_cam, R->K / R->D (in / out), delta (N x 6, nullable). Returns 1 when the call is finished.
+int hc_rcalib_end_pass(const double* acc231, const int32_t* cnt, int N, int C, int free_ext, int free_int,
+                       int param_mask, int pass, int I, int min_obs, int min_obs_cam, double lambda, double* T,
+                       mantis_rcalib_result* R, double* delta) {
+  return mk::rcalib::end_pass(acc231, cnt, N, C, (uint32_t)free_ext, (uint32_t)free_int, (uint32_t)param_mask, pass, I,
+                              min_obs, min_obs_cam, lambda, T, *R, delta)
+             ? 1 : 0;
+}
+// the whole call on the host: N views of C cameras (Tbc C x 16, K C x 9 rounded to float as the
+// library does, D C x 4, frames: N x C pointers to W x H frames of stride 3 W), rows summed in slot order
+void hc_rcalib_seq(const double* T_in, const double* Tbc, const double* K, const double* D, const uint8_t* const* frames,
+                   int N, int C, int W, int H, const double* X, int nw, int nr, int ng, const mantis_refine_params* p,
+                   const mantis_rcalib_params* rp, double* T_out, mantis_rcalib_result* out) {
+  namespace rf = mk::refine;
+  const int n = nw + nr + ng;
+  std::vector<uint8_t> flags(n > 0 ? n : 1);
+  rf::line_flags(X, n, p->landmark_pitch, flags.data());
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags.data(), n, cand.data());
+  std::vector<mk::Cam> cm(C);
+  for (int c = 0; c < C; c++) cm[c] = hc_cam(K + 9 * c, D + 4 * c);
+  mk::rcalib::rcalib_seq(T_in, Tbc, cm.data(), frames, N, C, W, H, X, nw, nr, cand.data(), nc, *p, *rp, T_out, *out,
+                         nullptr);
+}
+// the gate, rms_cam and the covariances (rcalib::conclude) of a result record with the last pass's acc231 / counts
+void hc_rcalib_conclude(const double* acc231, const int32_t* cnt, int N, int C, int free_ext, int free_int,
+                        int param_mask, int min_obs, int min_obs_cam, double max_rms, mantis_rcalib_result* R) {
+  mk::rcalib::conclude(acc231, cnt, N, C, (uint32_t)free_ext, (uint32_t)free_int, (uint32_t)param_mask, min_obs,
+                       min_obs_cam, max_rms, *R);
+}
+int hc_sizeof_rcalib_params(void) { return (int)sizeof(mantis_rcalib_params); }
+int hc_sizeof_rcalib_result(void) { return (int)sizeof(mantis_rcalib_result); }
 
 // The modes refined (mk_mcl_refine.h): the rules mantis_mcl_refine_modes and k_mcl_recentre run.
 // modes: a struct mantis_mcl_modes; T_ref 8 x 16 (row-major), refined 8; out: key_kept / applied (8
