@@ -149,8 +149,7 @@ def seq(T_in, exts, frames, lm, p, cp, K=None, D=None):
         K, D = synth.intrinsics(w, h)
     T = np.ascontiguousarray(np.array(T_in, np.float64).reshape(N, 16))
     E = np.ascontiguousarray(np.array(exts, np.float64).reshape(Cn, 16))
-    Ks = np.ascontiguousarray(np.tile(np.asarray(K, np.float64).reshape(9), (Cn, 1)))
-    Ds = np.ascontiguousarray(np.tile(np.asarray(D, np.float64).reshape(4), (Cn, 1)))
+    Ks, Ds = RR.per_camera(K, D, Cn)
     keep = [np.ascontiguousarray(frames[r][c], np.uint8) for r in range(N) for c in range(Cn)]
     ptrs = (C.c_void_p * (N * Cn))(*[k.ctypes.data for k in keep])
     T_out = np.zeros((N, 4, 4))

@@ -83,10 +83,11 @@ def np_dist(kd, x, y):
     return x * cd * kd[0] + kd[2], y * cd * kd[1] + kd[3]
 
 
-def model_gap(kd, kd_true, w=W, h=H_):
+def model_gap(kd, kd_true, w=W, h=H_, span=(2.2, 1.3)):
     """rms over the 23 x 14 grid of normalized points whose true image lies in the frame of
-    |dist_kd - dist_true|, in pixels."""
-    gx, gy = np.meshgrid(np.linspace(-2.2, 2.2, 23), np.linspace(-1.3, 1.3, 14))
+    |dist_kd - dist_true|, in pixels. span: the grid's half extent (the bench lens's field; a narrower lens
+    needs a narrower grid to keep its points in the frame)."""
+    gx, gy = np.meshgrid(np.linspace(-span[0], span[0], 23), np.linspace(-span[1], span[1], 14))
     ut, vt = np_dist(kd_true, gx, gy)
     inside = (ut >= 0) & (ut <= w - 1) & (vt >= 0) & (vt <= h - 1)
     assert inside.sum() > 100

@@ -120,8 +120,29 @@ def solve6(acc, lam, T):
     return bool(ok), Tn, d6
 
 
+def per_camera(K, D, Cn):
+    """(Ks [Cn, 9], Ds [Cn, 4]) from one K (3 x 3) and D (4) for every camera, or from one of each per camera."""
+    Ks, Ds = np.asarray(K, np.float64).reshape(-1, 9), np.asarray(D, np.float64).reshape(-1, 4)
+    if len(Ks) == 1:
+        Ks = np.tile(Ks, (Cn, 1))
+    if len(Ds) == 1:
+        Ds = np.tile(Ds, (Cn, 1))
+    assert Ks.shape == (Cn, 9) and Ds.shape == (Cn, 4)
+    return np.ascontiguousarray(Ks), np.ascontiguousarray(Ds)
+
+
+def lenses(n, w, h, Ks=None, Ds=None):
+    """Per-camera (Ks, Ds) of the GPU checkers: the bench lens of the frame size for every camera unless they
+    are given."""
+    if Ks is None:
+        K, D = synth.intrinsics(w, h)
+        Ks, Ds = [K] * n, [D] * n
+    assert len(Ks) == len(Ds) == n
+    return Ks, Ds
+
+
 def seq(T_in, exts, imgs, X, nw, nr, ng, p, K=None, D=None):
-    """hc_refine_seq on one rig: a MantisRefineResult."""
+    """hc_refine_seq on one rig: a MantisRefineResult. K, D: one for every camera, or one per camera."""
     import mantis_amd as M
 
     Cn = len(imgs)
@@ -130,8 +151,7 @@ def seq(T_in, exts, imgs, X, nw, nr, ng, p, K=None, D=None):
         K, D = synth.intrinsics(w, h)
     T = np.ascontiguousarray(T_in, np.float64)
     E = np.ascontiguousarray(np.array(exts, np.float64).reshape(Cn, 16))
-    Ks = np.ascontiguousarray(np.tile(np.asarray(K, np.float64).reshape(9), (Cn, 1)))
-    Ds = np.ascontiguousarray(np.tile(np.asarray(D, np.float64).reshape(4), (Cn, 1)))
+    Ks, Ds = per_camera(K, D, Cn)
     keep = [np.ascontiguousarray(i, np.uint8) for i in imgs]
     ptrs = (C.c_void_p * Cn)(*[k.ctypes.data for k in keep])
     out = M.MantisRefineResult()

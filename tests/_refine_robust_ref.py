@@ -108,8 +108,7 @@ def seq_robust(T_in, exts, imgs, X, nw, nr, ng, p, rb, K=None, D=None):
         K, D = synth.intrinsics(w, h)
     T = np.ascontiguousarray(T_in, np.float64)
     E = np.ascontiguousarray(np.array(exts, np.float64).reshape(Cn, 16))
-    Ks = np.ascontiguousarray(np.tile(np.asarray(K, np.float64).reshape(9), (Cn, 1)))
-    Ds = np.ascontiguousarray(np.tile(np.asarray(D, np.float64).reshape(4), (Cn, 1)))
+    Ks, Ds = RR.per_camera(K, D, Cn)
     keep = [np.ascontiguousarray(i, np.uint8) for i in imgs]
     ptrs = (C.c_void_p * Cn)(*[k.ctypes.data for k in keep])
     out, st = M.MantisRefineResult(), M.MantisRefineRobustStats()

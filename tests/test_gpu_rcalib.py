@@ -52,14 +52,16 @@ def scene():
     return QR.joint_scene()
 
 
-def _images(frames, exts, K=None, D=None):
-    """frames[r][c] -> view-major mantis_images, every view with the rig's extrinsics and nominal intrinsics."""
+def _images(frames, exts, K=None, D=None, Ks=None, Ds=None):
+    """frames[r][c] -> view-major mantis_images, every view with the rig's extrinsics and nominal intrinsics
+    (K, D for every camera, or Ks, Ds per camera; default: the bench lens)."""
     import mantis_amd as M
 
     h, w = frames[0][0].shape[:2]
-    if K is None:
-        K, D = synth.intrinsics(w, h)
-    return [M.make_image(f, K, D, T_base_cam=exts[c]) for fr in frames for c, f in enumerate(fr)]
+    if K is not None:
+        Ks, Ds = [K] * len(exts), [D] * len(exts)
+    Ks, Ds = RR.lenses(len(exts), w, h, Ks, Ds)
+    return [M.make_image(f, Ks[c], Ds[c], T_base_cam=exts[c]) for fr in frames for c, f in enumerate(fr)]
 
 
 def _cond_S(Hm, N):
@@ -67,22 +69,28 @@ def _cond_S(Hm, N):
     return np.linalg.cond(Hm[n:, n:] - Hm[n:, :n] @ np.linalg.solve(Hm[:n, :n], Hm[:n, n:]))
 
 
-def _check_call(m, lm, frames, exts, T0s, fe, fi, mask=0xFF, landmarks=None, min_obs_cam=None, **params):
-    """One call with record = 1: every pass against the host rules; returns (T_out, result)."""
+def _check_call(m, lm, frames, exts, T0s, fe, fi, mask=0xFF, landmarks=None, min_obs_cam=None, Ks=None, Ds=None,
+                whole_call=True, slot_guard=None, cap=0.005, gap_span=(2.2, 1.3), **params):
+    """One call with record = 1: every pass against the host rules; returns (T_out, result). Ks, Ds: per-camera
+    lenses (default: the bench lens); whole_call = False leaves out the comparison with hc_rcalib_seq;
+    slot_guard(T, E, kd, img, f, free_ext, free_int, mask, p) replaces QR.obs and returns its five arrays with
+    the slots it leaves out added to the tie flag (1 = a tie, which also drops the whole-call comparison as
+    ever; 2 = left out of the row comparison only); cap is the share of flagged slots allowed
+    (tests/_line_cases.py)."""
     X, nw, nr, ng = landmarks or lm
     N, Cn = len(frames), len(exts)
     h, w = frames[0][0].shape[:2]
-    K, D = synth.intrinsics(w, h)
-    kd0 = np.tile(IR.kd_of(K, D), (Cn, 1))
+    Ks, Ds = RR.lenses(Cn, w, h, Ks, Ds)
+    kd0 = np.array([IR.kd_of(K, D) for K, D in zip(Ks, Ds)])
     ext0 = np.ascontiguousarray(np.array(exts, np.float64))
-    T_out, res = m.calibrate_rig(_images(frames, exts), N, np.array(T0s), fe, fi, param_mask=mask,
+    T_out, res = m.calibrate_rig(_images(frames, exts, Ks=Ks, Ds=Ds), N, np.array(T0s), fe, fi, param_mask=mask,
                                  min_obs_cam=min_obs_cam, record=1, **params)
     p = m.refine_params(**params)
     rp = QR.rcalib_params(fe, fi, mask, min_obs_cam)
     f = RR.flags(X, p.landmark_pitch)
     nc = len(RR.candidates(f))
     assert (res.n_cand, res.n_rigs, res.n_cams, res.free_ext, res.free_int, res.param_mask) == (nc, N, Cn, fe, fi, mask)
-    flagged = total = 0
+    flagged = ties = total = 0
     Ts, Es, KDs, accs, cnts = [], [], [], [], []
     for k in range(res.iterations_run + 1):
         Tk, acck, cntk = [], np.zeros((N, Cn, QR.ACC)), np.zeros((N, Cn), np.int32)
@@ -95,12 +103,17 @@ def _check_call(m, lm, frames, exts, T0s, fe, fi, mask=0xFF, landmarks=None, min
             assert np.array_equal(KD, KDs[k]) and np.array_equal(E, Es[k]), "one rig per pass"
             assert codes.shape == (Cn * nc,)
             for c in range(Cn):
-                hc_, hSw, hSkw, hrows, tie = QR.obs(T, E[c], KD[c], frames[r][c], X, nw, nr, ng, f, fe >> c & 1,
-                                                    fi >> c & 1, mask, R=p.half_window, white_thresh=p.white_thresh,
-                                                    min_weight=p.min_weight)
+                if slot_guard is None:
+                    hc_, hSw, hSkw, hrows, tie = QR.obs(T, E[c], KD[c], frames[r][c], X, nw, nr, ng, f, fe >> c & 1,
+                                                        fi >> c & 1, mask, R=p.half_window,
+                                                        white_thresh=p.white_thresh, min_weight=p.min_weight)
+                else:
+                    hc_, hSw, hSkw, hrows, tie = slot_guard(T, E[c], KD[c], frames[r][c], f, fe >> c & 1,
+                                                            fi >> c & 1, mask, p)
                 sl = slice(c * nc, (c + 1) * nc)
                 ok = tie == 0
                 flagged += int((~ok).sum())
+                ties += int((tie == 1).sum())
                 total += nc
                 where = f"pass {k} view {r} camera {c}"
                 assert np.array_equal(codes[sl][ok], hc_[ok]), where
@@ -128,7 +141,7 @@ def _check_call(m, lm, frames, exts, T0s, fe, fi, mask=0xFF, landmarks=None, min
         assert res.n_obs[k] == n_obs and list(res.n_obs_cam[k])[:Cn] == list(cntk.sum(axis=0))
         rr = sum(acck.reshape(-1, QR.ACC)[:, QR.ACC - 1].tolist())  # (view, camera) order
         assert res.rms[k] == (math.sqrt(rr / n_obs) if n_obs else 0.0)
-    assert flagged <= 0.005 * total, (flagged, total)
+    assert flagged <= cap * total, (flagged, total)
     assert np.array_equal(Ts[0], np.array(T0s)) and np.array_equal(KDs[0], kd0) and np.array_equal(Es[0], ext0), \
         "pass 0 observes the inputs"
     cond_S = 0.0
@@ -157,15 +170,17 @@ def _check_call(m, lm, frames, exts, T0s, fe, fi, mask=0xFF, landmarks=None, min
         assert QR.kds_of(res)[c][held].tobytes() == kd0[c][held].tobytes()
         if not fe >> c & 1:
             assert QR.exts_of(res)[c].tobytes() == ext0[c].tobytes()
-    if flagged == 0:
-        hT, host = QR.seq(T0s, exts, [K] * Cn, [D] * Cn, frames, (X, nw, nr, ng), p, rp)
+    if ties and whole_call:
+        print(f"whole call not compared: {ties} slots within 1e-9 of a rounding tie")
+    if ties == 0 and whole_call:
+        hT, host = QR.seq(T0s, exts, Ks, Ds, frames, (X, nw, nr, ng), p, rp)
         assert (res.iterations_run, res.status) == (host.iterations_run, host.status)
         assert list(res.n_obs) == list(host.n_obs)
         assert np.array_equal(np.array(res.n_obs_cam), np.array(host.n_obs_cam))
         if res.status == 0:
             dT = np.abs(T_out - hT).max()
             dE = np.abs(QR.exts_of(res) - QR.exts_of(host)).max()
-            gap = max(IR.model_gap(QR.kds_of(res)[c], QR.kds_of(host)[c], w, h) for c in range(Cn))
+            gap = max(IR.model_gap(QR.kds_of(res)[c], QR.kds_of(host)[c], w, h, gap_span) for c in range(Cn))
             print(f"whole call against the host: cond(S) {cond_S:.3g} poses {dT:.3g} extrinsics {dE:.3g} gap {gap:.3g} px")
             if cond_S <= COND_MAX:
                 assert dT <= POSE_TOL and dE <= POSE_TOL and gap < GAP_TOL

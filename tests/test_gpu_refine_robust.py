@@ -63,22 +63,23 @@ def ring8():
     return RR.rig_scene(8, 1)
 
 
-def _images(frames, exts, w=W, h=H):
+def _images(frames, exts, w=W, h=H, Ks=None, Ds=None):
     import mantis_amd as M
 
-    K, D = synth.intrinsics(w, h)
-    return [M.make_image(f, K, D, T_base_cam=e) for f, e in zip(frames, exts)]
+    Ks, Ds = RR.lenses(len(frames), w, h, Ks, Ds)
+    return [M.make_image(f, K, D, T_base_cam=e) for f, e, K, D in zip(frames, exts, Ks, Ds)]
 
 
-def _check_call(m, lm, frames, exts, T0, loss, landmarks=None, **params):
-    """One rig with the robust rows on, record = 1: every pass against the host rules; (result, stats)."""
+def _check_call(m, lm, frames, exts, T0, loss, landmarks=None, Ks=None, Ds=None, **params):
+    """One rig with the robust rows on, record = 1: every pass against the host rules; (result, stats).
+    Ks, Ds: per-camera lenses (default: the bench lens)."""
     X, nw, nr, ng = landmarks or lm
     h, w = frames[0].shape[:2]
-    K, D = synth.intrinsics(w, h)
     Cn = len(frames)
+    Ks, Ds = RR.lenses(Cn, w, h, Ks, Ds)
     rb = RB.robust_params(loss)
     m.set_refine_robust(loss)
-    res = m.refine_batch(_images(frames, exts, w, h), 1, T0, record=1, **params)[0]
+    res = m.refine_batch(_images(frames, exts, w, h, Ks, Ds), 1, T0, record=1, **params)[0]
     st = m.refine_robust_stats(0)
     assert st.loss == rb.loss
     p = m.refine_params(**params)
@@ -95,8 +96,9 @@ def _check_call(m, lm, frames, exts, T0, loss, landmarks=None, **params):
         assert codes.shape == keys.shape == wts.shape == (Cn * nc,)
         # the plain record still holds the unweighted rows: the host's, at the device's pose
         for c in range(Cn):
-            hc_, hSw, hSkw, hrows, tie = RR.obs(T, exts[c], K, D, frames[c], X, nw, nr, ng, f, R=p.half_window,
-                                                 white_thresh=p.white_thresh, min_weight=p.min_weight)
+            hc_, hSw, hSkw, hrows, tie = RR.obs(T, exts[c], Ks[c], Ds[c], frames[c], X, nw, nr, ng, f,
+                                                 R=p.half_window, white_thresh=p.white_thresh,
+                                                 min_weight=p.min_weight)
             sl = slice(c * nc, (c + 1) * nc)
             ok = tie == 0
             flagged += int((~ok).sum())
@@ -129,7 +131,7 @@ def _check_call(m, lm, frames, exts, T0, loss, landmarks=None, **params):
         np.testing.assert_allclose(np.array(res.delta[k]), d6, rtol=0, atol=1e-12)
     np.testing.assert_allclose(np.array(res.T_w_b).reshape(4, 4), Ts[-1], rtol=0, atol=0)
     if flagged == 0:
-        host, hst = RB.seq_robust(T0, exts, frames, X, nw, nr, ng, p, rb, K, D)
+        host, hst = RB.seq_robust(T0, exts, frames, X, nw, nr, ng, p, rb, Ks, Ds)
         np.testing.assert_allclose(np.array(res.T_w_b), np.array(host.T_w_b), rtol=0, atol=POSE_TOL)
         assert list(res.n_obs) == list(host.n_obs)
         assert (res.iterations_run, res.refined, res.status) == (host.iterations_run, host.refined, host.status)
