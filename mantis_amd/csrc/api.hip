@@ -359,45 +359,23 @@ struct Ctx {
     size_t rslot_cap = 0;
     int rec_loss = 0;  // the last call's loss
   } rf;
-  // extrinsic calibration (calib_impl.hip): workspaces grown to the largest call
-  // (per-view buffers hold view_cap views of 8 cameras) and the last call's shape
-  // (mantis_get_calib_record)
-  struct Calib {
-    void *d_state = nullptr, *h_state = nullptr;  // CalibState; h: pinned, with the poses, accumulators and counts behind it
+  // the three calibrations (linecal_impl.hip): workspaces grown to the largest call of their
+  // kind (per-view buffers hold view_cap views of 8 cameras) and the last call's shape
+  // (mantis_get_calib_record / _icalib_ / _rcalib_). One instance per kind, so a call of one
+  // kind leaves the last record of the others readable. lds_ok: k_linecal_solve may take its
+  // dynamic LDS (asked once, by the rig calibration only)
+  struct Linecal {
+    void *d_state = nullptr, *h_state = nullptr;  // LinecalState; h: pinned, with the poses, accumulators and counts behind it
     double *d_T = nullptr, *d_acc = nullptr, *d_Y = nullptr, *d_Wt = nullptr;
     int32_t *d_cnt = nullptr, *d_pd = nullptr;
-    double *d_recT = nullptr, *d_recE = nullptr, *d_recAcc = nullptr;  // [pass][view][16], [pass][C][16], [pass][view][C][91]
-    void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
-    int view_cap = 0;
-    size_t slot_cap = 0, racc_cap = 0;
-    int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
-  } cb;
-  // intrinsic calibration (icalib_impl.hip): as `cb`, with the passes' intrinsics in place of the extrinsics
-  // (mantis_get_icalib_record)
-  struct Icalib {
-    void *d_state = nullptr, *h_state = nullptr;  // IcalibState; h: pinned, with the poses, accumulators and counts behind it
-    double *d_T = nullptr, *d_acc = nullptr, *d_Y = nullptr, *d_Wt = nullptr;
-    int32_t *d_cnt = nullptr, *d_pd = nullptr;
-    double *d_recT = nullptr, *d_recKD = nullptr, *d_recAcc = nullptr;  // [pass][view][16], [pass][C][8], [pass][view][C][120]
-    void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
-    int view_cap = 0;
-    size_t slot_cap = 0, racc_cap = 0;
-    int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
-  } ib;
-  // rig calibration (rcalib_impl.hip): as `cb` and `ib` together, with the passes' extrinsics and intrinsics
-  // (mantis_get_rcalib_record); lds_ok: k_rcalib_solve may take its dynamic LDS (asked once)
-  struct Rcalib {
-    void *d_state = nullptr, *h_state = nullptr;  // RcalibState; h: pinned, with the poses, accumulators and counts behind it
-    double *d_T = nullptr, *d_acc = nullptr, *d_Y = nullptr, *d_Wt = nullptr;
-    int32_t *d_cnt = nullptr, *d_pd = nullptr;
-    // [pass][view][16], [pass][C][16], [pass][C][8], [pass][view][C][231]
+    // [pass][view][16], [pass][C][16] (with J_ext), [pass][C][8] (with J_int), [pass][view][C][kAcc]
     double *d_recT = nullptr, *d_recE = nullptr, *d_recKD = nullptr, *d_recAcc = nullptr;
     void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
     int view_cap = 0;
     size_t slot_cap = 0, racc_cap = 0;
     bool lds_asked = false, lds_ok = false;
     int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
-  } rb;
+  } cb, ib, rb;  // extrinsic, intrinsic, rig
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1460,21 +1438,13 @@ mantis_status mantis_destroy(void* ctx) {
     if (p) (void)hipFree(p);
   if (c->rf.h_state) (void)hipHostFree(c->rf.h_state);
   if (c->rf.h_rstats) (void)hipHostFree(c->rf.h_rstats);
-  void* cptrs[] = {c->cb.d_state, c->cb.d_T, c->cb.d_acc, c->cb.d_Y, c->cb.d_Wt, c->cb.d_cnt, c->cb.d_pd,
-                   c->cb.d_recT, c->cb.d_recE, c->cb.d_recAcc, c->cb.d_slots};
-  for (void* p : cptrs)
-    if (p) (void)hipFree(p);
-  if (c->cb.h_state) (void)hipHostFree(c->cb.h_state);
-  void* iptrs[] = {c->ib.d_state, c->ib.d_T, c->ib.d_acc, c->ib.d_Y, c->ib.d_Wt, c->ib.d_cnt, c->ib.d_pd,
-                   c->ib.d_recT, c->ib.d_recKD, c->ib.d_recAcc, c->ib.d_slots};
-  for (void* p : iptrs)
-    if (p) (void)hipFree(p);
-  if (c->ib.h_state) (void)hipHostFree(c->ib.h_state);
-  void* bptrs[] = {c->rb.d_state, c->rb.d_T, c->rb.d_acc, c->rb.d_Y, c->rb.d_Wt, c->rb.d_cnt, c->rb.d_pd,
-                   c->rb.d_recT, c->rb.d_recE, c->rb.d_recKD, c->rb.d_recAcc, c->rb.d_slots};
-  for (void* p : bptrs)
-    if (p) (void)hipFree(p);
-  if (c->rb.h_state) (void)hipHostFree(c->rb.h_state);
+  for (Ctx::Linecal* k : {&c->cb, &c->ib, &c->rb}) {
+    void* kptrs[] = {k->d_state, k->d_T, k->d_acc, k->d_Y, k->d_Wt, k->d_cnt, k->d_pd,
+                     k->d_recT, k->d_recE, k->d_recKD, k->d_recAcc, k->d_slots};
+    for (void* p : kptrs)
+      if (p) (void)hipFree(p);
+    if (k->h_state) (void)hipHostFree(k->h_state);
+  }
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
                    c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes, c->mcl.h_moved};
@@ -2334,8 +2304,6 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "mcl_modes_impl.hip"
 #include "mcl_color_impl.hip"
 #include "refine_impl.hip"
-#include "calib_impl.hip"
-#include "icalib_impl.hip"
-#include "rcalib_impl.hip"
+#include "linecal_impl.hip"
 #include "mcl_refine_impl.hip"
 #include "ros_wire.h"

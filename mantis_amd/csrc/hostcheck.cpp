@@ -13,9 +13,7 @@
 static int g_jacobi_ff = 1;
 #define MK_JACOBI_FF g_jacobi_ff
 #include "mk_bits.h"
-#include "mk_calib.h"
-#include "mk_icalib.h"
-#include "mk_rcalib.h"
+#include "mk_linecal.h"
 #include "mk_contour.h"
 #include "mk_gn.h"
 #include "mk_math.h"
@@ -661,18 +659,25 @@ int hc_refine_end_pass_robust(const double* acc28, int n_obs, int n_pos, int pas
 int hc_sizeof_refine_robust_params(void) { return (int)sizeof(mantis_refine_robust_params); }
 int hc_sizeof_refine_robust_stats(void) { return (int)sizeof(mantis_refine_robust_stats); }
 
-// Extrinsic calibration (mk_calib.h): the rules k_calib_obs / k_calib_rig / k_calib_solve run.
-// hc_refine_obs with rows of 13 ([J_pose | J_ext | r]; J_ext zeros unless free_cam)
-int hc_calib_obs(const double* Twb, const double* Tbc, const double* K, const double* D, const uint8_t* bgr, int W,
-                 int H, const double* X, int nw, int nr, int ng, const uint8_t* flags, int R, int white_thresh,
-                 int min_weight, int free_cam, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, int32_t* tie) {
+// The three calibrations (mk_linecal.h): the rules k_linecal_obs / k_linecal_rig / k_linecal_solve run,
+// at the problem P (linecal::Ext / Int / Rig). The hc_calib_* and hc_icalib_* entries take the public
+// structs of the single calibrations and widen / narrow them around the shared rules.
+extern "C++" {
+namespace {
+namespace lc = mk::linecal;
+
+// hc_refine_obs at the intrinsics cm with rows of P::kRow ([J_pose | J_ext | J_int | r]; J_ext zeros unless
+// free_ext, J_int zeros unless free_int, a zero for a parameter outside param_mask)
+template <class P>
+int lc_obs(const double* Twb, const double* Tbc, const mk::Cam& cm, const uint8_t* bgr, int W, int H, const double* X,
+           int nw, int nr, int ng, const uint8_t* flags, int R, int white_thresh, int min_weight, int free_ext,
+           int free_int, int param_mask, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, int32_t* tie) {
   namespace rf = mk::refine;
   const int n = nw + nr + ng;
   std::vector<int32_t> cand(n > 0 ? n : 1);
   const int nc = rf::candidates(flags, n, cand.data());
   mk::GnCam gc;
   rf::gncam_from(Tbc, gc);
-  const mk::Cam cm = hc_cam(K, D);
   double Rt[9], t[3];
   rf::pose_parts(Twb, Rt, t);
   const rf::Window win{R, white_thresh, min_weight, 0};
@@ -680,188 +685,138 @@ int hc_calib_obs(const double* Twb, const double* Tbc, const double* K, const do
     const int i = cand[k] & 0xffff, axis = cand[k] >> 16;
     int tg[3], near = 0;
     rf::target_bgr(i, nw, nr, tg);
-    mk::calib::Slot o;
-    mk::calib::observe(Rt, t, gc, cm, bgr, W, H, X + 3 * i, axis, tg, win, free_cam != 0, o, &near);
+    typename P::Slot o;
+    P::observe(Rt, t, gc, cm, bgr, W, H, X + 3 * i, axis, tg, win, free_ext != 0, free_int != 0, (uint32_t)param_mask, o,
+               &near);
     codes[k] = o.code;
     Sw[k] = o.Sw;
     Skw[k] = o.Skw;
-    std::memcpy(rows + 13 * k, o.row, sizeof(o.row));
+    std::memcpy(rows + P::kRow * k, o.row, sizeof(o.row));
     if (tie) tie[k] = near;
   }
   return nc;
 }
-// acc91 of n rows of 13 doubles, summed in row order
-void hc_calib_accumulate(const double* rows, int n, double* acc91) {
-  for (int e = 0; e < mk::calib::kAcc; e++) acc91[e] = 0.0;
-  for (int k = 0; k < n; k++) mk::calib::accumulate_row(rows + 13 * k, acc91);
+// the accumulator of n rows of P::kRow doubles, summed in row order
+template <class P>
+void lc_accumulate(const double* rows, int n, double* acc) {
+  for (int e = 0; e < P::kAcc; e++) acc[e] = 0.0;
+  for (int k = 0; k < n; k++) P::accumulate_row(rows + P::kRow * k, acc);
 }
+// the whole call on the host: N views of C cameras (Tbc C x 16, K C x 9 rounded to float as the
+// library does, D C x 4, frames: N x C pointers to W x H frames of stride 3 W), rows summed in slot order
+template <class P>
+void lc_seq(const double* T_in, const double* Tbc, const double* K, const double* D, const uint8_t* const* frames, int N,
+            int C, int W, int H, const double* X, int nw, int nr, int ng, const mantis_refine_params* p, uint32_t fe,
+            uint32_t fi, uint32_t pm, int32_t min_obs_cam, double* T_out, mantis_rcalib_result* out) {
+  namespace rf = mk::refine;
+  const int n = nw + nr + ng;
+  std::vector<uint8_t> flags(n > 0 ? n : 1);
+  rf::line_flags(X, n, p->landmark_pitch, flags.data());
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags.data(), n, cand.data());
+  std::vector<mk::Cam> cm(C);
+  for (int c = 0; c < C; c++) cm[c] = hc_cam(K + 9 * c, D + 4 * c);
+  P::seq(T_in, Tbc, cm.data(), frames, N, C, W, H, X, nw, nr, cand.data(), nc, *p, fe, fi, pm, min_obs_cam, T_out, *out,
+         nullptr);
+}
+}  // namespace
+}  // extern "C++"
+
+// Extrinsic calibration: rows of 13, acc91; K, D as hc_refine_obs takes them
+int hc_calib_obs(const double* Twb, const double* Tbc, const double* K, const double* D, const uint8_t* bgr, int W,
+                 int H, const double* X, int nw, int nr, int ng, const uint8_t* flags, int R, int white_thresh,
+                 int min_weight, int free_cam, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, int32_t* tie) {
+  return lc_obs<lc::Ext>(Twb, Tbc, hc_cam(K, D), bgr, W, H, X, nw, nr, ng, flags, R, white_thresh, min_weight, free_cam,
+                         0, 0, codes, Sw, Skw, rows, tie);
+}
+void hc_calib_accumulate(const double* rows, int n, double* acc91) { lc_accumulate<lc::Ext>(rows, n, acc91); }
 // the end of a pass from given accumulators (N x C x 91) and counts (N x C): T (N x 16, in / out),
 // R->T_base_cam (in / out), delta (N x 6, nullable). Returns 1 when the call is finished.
 int hc_calib_end_pass(const double* acc91, const int32_t* cnt, int N, int C, int free_cams, int pass, int I, int min_obs,
                       int min_obs_cam, double lambda, double* T, mantis_calib_result* R, double* delta) {
-  return mk::calib::end_pass(acc91, cnt, N, C, (uint32_t)free_cams, pass, I, min_obs, min_obs_cam, lambda, T, *R, delta)
-             ? 1 : 0;
+  return lc::with_state(*R, [&](mantis_rcalib_result& w) {
+    return lc::Ext::end_pass(acc91, cnt, N, C, (uint32_t)free_cams, 0u, 0u, pass, I, min_obs, min_obs_cam, lambda, T, w,
+                             delta) ? 1 : 0;
+  });
 }
-// the whole call on the host: N views of C cameras (Tbc C x 16, K C x 9, D C x 4, frames: N x C
-// pointers to W x H frames of stride 3 W), rows summed in slot order
 void hc_calib_seq(const double* T_in, const double* Tbc, const double* K, const double* D, const uint8_t* const* frames,
                   int N, int C, int W, int H, const double* X, int nw, int nr, int ng, const mantis_refine_params* p,
                   const mantis_calib_params* cp, double* T_out, mantis_calib_result* out) {
-  namespace rf = mk::refine;
-  const int n = nw + nr + ng;
-  std::vector<uint8_t> flags(n > 0 ? n : 1);
-  rf::line_flags(X, n, p->landmark_pitch, flags.data());
-  std::vector<int32_t> cand(n > 0 ? n : 1);
-  const int nc = rf::candidates(flags.data(), n, cand.data());
-  std::vector<mk::Cam> cm(C);
-  for (int c = 0; c < C; c++) cm[c] = hc_cam(K + 9 * c, D + 4 * c);
-  mk::calib::calib_seq(T_in, Tbc, cm.data(), frames, N, C, W, H, X, nw, nr, cand.data(), nc, *p, *cp, T_out, *out,
-                       nullptr);
+  mantis_rcalib_result w;
+  lc_seq<lc::Ext>(T_in, Tbc, K, D, frames, N, C, W, H, X, nw, nr, ng, p, (uint32_t)cp->free_cams, 0u, 0u,
+                  cp->min_obs_cam, T_out, &w);
+  lc::narrow(w, *out);
 }
-// the gate, rms_cam and the covariances (calib::conclude) of a result record with the last pass's acc91 / counts
+// the gate, rms_cam and the covariances (conclude) of a result record with the last pass's acc91 / counts
 void hc_calib_conclude(const double* acc91, const int32_t* cnt, int N, int C, int free_cams, int min_obs,
                        int min_obs_cam, double max_rms, mantis_calib_result* R) {
-  mk::calib::conclude(acc91, cnt, N, C, (uint32_t)free_cams, min_obs, min_obs_cam, max_rms, *R);
+  lc::with_state(*R, [&](mantis_rcalib_result& w) {
+    lc::Ext::conclude(acc91, cnt, N, C, (uint32_t)free_cams, 0u, 0u, min_obs, min_obs_cam, max_rms, w);
+  });
 }
 int hc_sizeof_calib_params(void) { return (int)sizeof(mantis_calib_params); }
 int hc_sizeof_calib_result(void) { return (int)sizeof(mantis_calib_result); }
 
-// Intrinsic calibration (mk_icalib.h): the rules k_icalib_obs / k_icalib_rig / k_icalib_solve run.
-// hc_refine_obs at the FP64 intrinsics KD (fx, fy, cx, cy, k1..k4, taken as given) with rows of 15
-// ([J_pose | J_int | r]; J_int zeros unless free_cam, a zero for a parameter outside param_mask)
+// Intrinsic calibration: rows of 15, acc120, at the FP64 intrinsics KD (fx, fy, cx, cy, k1..k4, taken as given)
 int hc_icalib_obs(const double* Twb, const double* Tbc, const double* KD, const uint8_t* bgr, int W, int H,
                   const double* X, int nw, int nr, int ng, const uint8_t* flags, int R, int white_thresh, int min_weight,
                   int free_cam, int param_mask, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, int32_t* tie) {
-  namespace rf = mk::refine;
-  const int n = nw + nr + ng;
-  std::vector<int32_t> cand(n > 0 ? n : 1);
-  const int nc = rf::candidates(flags, n, cand.data());
-  mk::GnCam gc;
-  rf::gncam_from(Tbc, gc);
-  const mk::Cam cm = mk::icalib::cam_of(KD, KD + 4);
-  double Rt[9], t[3];
-  rf::pose_parts(Twb, Rt, t);
-  const rf::Window win{R, white_thresh, min_weight, 0};
-  for (int k = 0; k < nc; k++) {
-    const int i = cand[k] & 0xffff, axis = cand[k] >> 16;
-    int tg[3], near = 0;
-    rf::target_bgr(i, nw, nr, tg);
-    mk::icalib::Slot o;
-    mk::icalib::observe(Rt, t, gc, cm, bgr, W, H, X + 3 * i, axis, tg, win, free_cam != 0, (uint32_t)param_mask, o,
-                        &near);
-    codes[k] = o.code;
-    Sw[k] = o.Sw;
-    Skw[k] = o.Skw;
-    std::memcpy(rows + 15 * k, o.row, sizeof(o.row));
-    if (tie) tie[k] = near;
-  }
-  return nc;
+  return lc_obs<lc::Int>(Twb, Tbc, mk::icalib::cam_of(KD, KD + 4), bgr, W, H, X, nw, nr, ng, flags, R, white_thresh,
+                         min_weight, 0, free_cam, param_mask, codes, Sw, Skw, rows, tie);
 }
-// acc120 of n rows of 15 doubles, summed in row order
-void hc_icalib_accumulate(const double* rows, int n, double* acc120) {
-  for (int e = 0; e < mk::icalib::kAcc; e++) acc120[e] = 0.0;
-  for (int k = 0; k < n; k++) mk::icalib::accumulate_row(rows + 15 * k, acc120);
-}
-// the end of a pass from given accumulators (N x C x 120) and counts (N x C): T (N x 16, in / out),
-// R->K / R->D (in / out), delta (N x 6, nullable). Returns 1 when the call is finished.
+void hc_icalib_accumulate(const double* rows, int n, double* acc120) { lc_accumulate<lc::Int>(rows, n, acc120); }
+// as hc_calib_end_pass, with R->K / R->D (in / out)
 int hc_icalib_end_pass(const double* acc120, const int32_t* cnt, int N, int C, int free_cams, int param_mask, int pass,
                        int I, int min_obs, int min_obs_cam, double lambda, double* T, mantis_icalib_result* R,
                        double* delta) {
-  return mk::icalib::end_pass(acc120, cnt, N, C, (uint32_t)free_cams, (uint32_t)param_mask, pass, I, min_obs,
-                              min_obs_cam, lambda, T, *R, delta)
-             ? 1 : 0;
+  return lc::with_state(*R, [&](mantis_rcalib_result& w) {
+    return lc::Int::end_pass(acc120, cnt, N, C, 0u, (uint32_t)free_cams, (uint32_t)param_mask, pass, I, min_obs,
+                             min_obs_cam, lambda, T, w, delta) ? 1 : 0;
+  });
 }
-// the whole call on the host: N views of C cameras (Tbc C x 16, K C x 9 rounded to float as the
-// library does, D C x 4, frames: N x C pointers to W x H frames of stride 3 W), rows summed in slot order
 void hc_icalib_seq(const double* T_in, const double* Tbc, const double* K, const double* D, const uint8_t* const* frames,
                    int N, int C, int W, int H, const double* X, int nw, int nr, int ng, const mantis_refine_params* p,
                    const mantis_icalib_params* ip, double* T_out, mantis_icalib_result* out) {
-  namespace rf = mk::refine;
-  const int n = nw + nr + ng;
-  std::vector<uint8_t> flags(n > 0 ? n : 1);
-  rf::line_flags(X, n, p->landmark_pitch, flags.data());
-  std::vector<int32_t> cand(n > 0 ? n : 1);
-  const int nc = rf::candidates(flags.data(), n, cand.data());
-  std::vector<mk::Cam> cm(C);
-  for (int c = 0; c < C; c++) cm[c] = hc_cam(K + 9 * c, D + 4 * c);
-  mk::icalib::icalib_seq(T_in, Tbc, cm.data(), frames, N, C, W, H, X, nw, nr, cand.data(), nc, *p, *ip, T_out, *out,
-                         nullptr);
+  mantis_rcalib_result w;
+  lc_seq<lc::Int>(T_in, Tbc, K, D, frames, N, C, W, H, X, nw, nr, ng, p, 0u, (uint32_t)ip->free_cams,
+                  (uint32_t)ip->param_mask, ip->min_obs_cam, T_out, &w);
+  lc::narrow(w, *out);
 }
-// the gate, rms_cam and the covariances (icalib::conclude) of a result record with the last pass's acc120 / counts
 void hc_icalib_conclude(const double* acc120, const int32_t* cnt, int N, int C, int free_cams, int param_mask,
                         int min_obs, int min_obs_cam, double max_rms, mantis_icalib_result* R) {
-  mk::icalib::conclude(acc120, cnt, N, C, (uint32_t)free_cams, (uint32_t)param_mask, min_obs, min_obs_cam, max_rms, *R);
+  lc::with_state(*R, [&](mantis_rcalib_result& w) {
+    lc::Int::conclude(acc120, cnt, N, C, 0u, (uint32_t)free_cams, (uint32_t)param_mask, min_obs, min_obs_cam, max_rms, w);
+  });
 }
 int hc_sizeof_icalib_params(void) { return (int)sizeof(mantis_icalib_params); }
 int hc_sizeof_icalib_result(void) { return (int)sizeof(mantis_icalib_result); }
 
-// Rig calibration (mk_rcalib.h): the rules k_rcalib_obs / k_rcalib_rig / k_rcalib_solve run.
-// hc_icalib_obs with rows of 21 ([J_pose | J_ext | J_int | r]; J_ext zeros unless free_ext, J_int zeros
-// unless free_int, a zero for a parameter outside param_mask)
+// Rig calibration: rows of 21, acc231; R->T_base_cam, R->K / R->D (in / out)
 int hc_rcalib_obs(const double* Twb, const double* Tbc, const double* KD, const uint8_t* bgr, int W, int H,
                   const double* X, int nw, int nr, int ng, const uint8_t* flags, int R, int white_thresh, int min_weight,
                   int free_ext, int free_int, int param_mask, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows,
                   int32_t* tie) {
-  namespace rf = mk::refine;
-  const int n = nw + nr + ng;
-  std::vector<int32_t> cand(n > 0 ? n : 1);
-  const int nc = rf::candidates(flags, n, cand.data());
-  mk::GnCam gc;
-  rf::gncam_from(Tbc, gc);
-  const mk::Cam cm = mk::icalib::cam_of(KD, KD + 4);
-  double Rt[9], t[3];
-  rf::pose_parts(Twb, Rt, t);
-  const rf::Window win{R, white_thresh, min_weight, 0};
-  for (int k = 0; k < nc; k++) {
-    const int i = cand[k] & 0xffff, axis = cand[k] >> 16;
-    int tg[3], near = 0;
-    rf::target_bgr(i, nw, nr, tg);
-    mk::rcalib::Slot o;
-    mk::rcalib::observe(Rt, t, gc, cm, bgr, W, H, X + 3 * i, axis, tg, win, free_ext != 0, free_int != 0,
-                        (uint32_t)param_mask, o, &near);
-    codes[k] = o.code;
-    Sw[k] = o.Sw;
-    Skw[k] = o.Skw;
-    std::memcpy(rows + mk::rcalib::kRow * k, o.row, sizeof(o.row));
-    if (tie) tie[k] = near;
-  }
-  return nc;
+  return lc_obs<lc::Rig>(Twb, Tbc, mk::icalib::cam_of(KD, KD + 4), bgr, W, H, X, nw, nr, ng, flags, R, white_thresh,
+                         min_weight, free_ext, free_int, param_mask, codes, Sw, Skw, rows, tie);
 }
-// acc231 of n rows of 21 doubles, summed in row order
-void hc_rcalib_accumulate(const double* rows, int n, double* acc231) {
-  for (int e = 0; e < mk::rcalib::kAcc; e++) acc231[e] = 0.0;
-  for (int k = 0; k < n; k++) mk::rcalib::accumulate_row(rows + mk::rcalib::kRow * k, acc231);
-}
-// the end of a pass from given accumulators (N x C x 231) and counts (N x C): T (N x 16, in / out),
-// R->T_base_cam, R->K / R->D (in / out), delta (N x 6, nullable). Returns 1 when the call is finished.
+void hc_rcalib_accumulate(const double* rows, int n, double* acc231) { lc_accumulate<lc::Rig>(rows, n, acc231); }
 int hc_rcalib_end_pass(const double* acc231, const int32_t* cnt, int N, int C, int free_ext, int free_int,
                        int param_mask, int pass, int I, int min_obs, int min_obs_cam, double lambda, double* T,
                        mantis_rcalib_result* R, double* delta) {
-  return mk::rcalib::end_pass(acc231, cnt, N, C, (uint32_t)free_ext, (uint32_t)free_int, (uint32_t)param_mask, pass, I,
-                              min_obs, min_obs_cam, lambda, T, *R, delta)
+  return lc::Rig::end_pass(acc231, cnt, N, C, (uint32_t)free_ext, (uint32_t)free_int, (uint32_t)param_mask, pass, I,
+                           min_obs, min_obs_cam, lambda, T, *R, delta)
              ? 1 : 0;
 }
-// the whole call on the host: N views of C cameras (Tbc C x 16, K C x 9 rounded to float as the
-// library does, D C x 4, frames: N x C pointers to W x H frames of stride 3 W), rows summed in slot order
 void hc_rcalib_seq(const double* T_in, const double* Tbc, const double* K, const double* D, const uint8_t* const* frames,
                    int N, int C, int W, int H, const double* X, int nw, int nr, int ng, const mantis_refine_params* p,
                    const mantis_rcalib_params* rp, double* T_out, mantis_rcalib_result* out) {
-  namespace rf = mk::refine;
-  const int n = nw + nr + ng;
-  std::vector<uint8_t> flags(n > 0 ? n : 1);
-  rf::line_flags(X, n, p->landmark_pitch, flags.data());
-  std::vector<int32_t> cand(n > 0 ? n : 1);
-  const int nc = rf::candidates(flags.data(), n, cand.data());
-  std::vector<mk::Cam> cm(C);
-  for (int c = 0; c < C; c++) cm[c] = hc_cam(K + 9 * c, D + 4 * c);
-  mk::rcalib::rcalib_seq(T_in, Tbc, cm.data(), frames, N, C, W, H, X, nw, nr, cand.data(), nc, *p, *rp, T_out, *out,
-                         nullptr);
+  lc_seq<lc::Rig>(T_in, Tbc, K, D, frames, N, C, W, H, X, nw, nr, ng, p, (uint32_t)rp->free_ext, (uint32_t)rp->free_int,
+                  (uint32_t)rp->param_mask, rp->min_obs_cam, T_out, out);
 }
-// the gate, rms_cam and the covariances (rcalib::conclude) of a result record with the last pass's acc231 / counts
 void hc_rcalib_conclude(const double* acc231, const int32_t* cnt, int N, int C, int free_ext, int free_int,
                         int param_mask, int min_obs, int min_obs_cam, double max_rms, mantis_rcalib_result* R) {
-  mk::rcalib::conclude(acc231, cnt, N, C, (uint32_t)free_ext, (uint32_t)free_int, (uint32_t)param_mask, min_obs,
-                       min_obs_cam, max_rms, *R);
+  lc::Rig::conclude(acc231, cnt, N, C, (uint32_t)free_ext, (uint32_t)free_int, (uint32_t)param_mask, min_obs,
+                    min_obs_cam, max_rms, *R);
 }
 int hc_sizeof_rcalib_params(void) { return (int)sizeof(mantis_rcalib_params); }
 int hc_sizeof_rcalib_result(void) { return (int)sizeof(mantis_rcalib_result); }

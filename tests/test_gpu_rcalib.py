@@ -1,5 +1,5 @@
 """Rig calibration on the GPU (mantis_calibrate_rig): every recorded pass
-against the host build of the same rules (mk_rcalib.h through hc_rcalib_obs,
+against the host build of the same rules (mk_linecal.h through hc_rcalib_obs,
 fed the device's own recorded poses, extrinsics and intrinsics so that a
 flipped tie cannot cascade), the three MFMA tiles' accumulators against numpy
 sums of the recorded rows, each step against hc_rcalib_end_pass on the device's

@@ -1,5 +1,5 @@
 // Stand-alone check of the extrinsic calibration's rules (mantis_amd/csrc/
-// mk_calib.h: one observation with its window over the frame edges and the
+// mk_linecal.h at the problem Ext, mk_calib.h: one observation with its window over the frame edges and the
 // extrinsic's columns, the end of a pass with its starved and both singular
 // exits, the gate and the covariance, the whole call for N = 1 and 3 views,
 // C = 2 and 8 cameras with seven free, R = 1 and 15) on small synthetic frames
@@ -14,10 +14,35 @@
 #include <cstring>
 #include <vector>
 
-#include "../mantis_amd/csrc/mk_calib.h"
+#include "../mantis_amd/csrc/mk_linecal.h"
 
 namespace rf = mk::refine;
 namespace cal = mk::calib;
+namespace lc = mk::linecal;
+using xc = lc::Ext;  // the shared rules at the extrinsic calibration's problem
+
+// the shared rules on the extrinsic calibration's public struct
+static bool end_pass(const double* acc, const int32_t* cnt, int N, int C, uint32_t fm, int pass, int I, int32_t min_obs,
+                     int32_t min_obs_cam, double lambda, double* T, mantis_calib_result& R, double* delta) {
+  return lc::with_state(R, [&](mantis_rcalib_result& w) {
+    return xc::end_pass(acc, cnt, N, C, fm, 0u, 0u, pass, I, min_obs, min_obs_cam, lambda, T, w, delta);
+  });
+}
+static void conclude(const double* acc, const int32_t* cnt, int N, int C, uint32_t fm, int32_t min_obs,
+                     int32_t min_obs_cam, double max_rms, mantis_calib_result& R) {
+  lc::with_state(R, [&](mantis_rcalib_result& w) {
+    xc::conclude(acc, cnt, N, C, fm, 0u, 0u, min_obs, min_obs_cam, max_rms, w);
+  });
+}
+static void calib_seq(const double* T_in, const double* Tbc, const mk::Cam* cams, const uint8_t* const* frames, int N,
+                      int C, int W, int H, const double* X, int nw, int nr, const int32_t* cand, int n_cand,
+                      const mantis_refine_params& p, const mantis_calib_params& cp, double* T_out, mantis_calib_result& R,
+                      xc::Slot* slots) {
+  mantis_rcalib_result w;
+  xc::seq(T_in, Tbc, cams, frames, N, C, W, H, X, nw, nr, cand, n_cand, p, (uint32_t)cp.free_cams, 0u, 0u, cp.min_obs_cam,
+          T_out, w, slots);
+  lc::narrow(w, R);
+}
 
 static int g_fail = 0;
 #define CHECK(cond)                                                  \
@@ -118,9 +143,9 @@ static void check_windows() {
         rf::Slot o7;
         rf::observe(Rt, t, gc, cam, img.data(), W, H, X, trial & 1, tg, win, o7, nullptr);
         for (int fr = 0; fr < 2; fr++) {
-          cal::Slot o;
+          xc::Slot o;
           int tie;
-          cal::observe(Rt, t, gc, cam, img.data(), W, H, X, trial & 1, tg, win, fr != 0, o, &tie);
+          xc::observe(Rt, t, gc, cam, img.data(), W, H, X, trial & 1, tg, win, fr != 0, false, 0u, o, &tie);
           CHECK(o.code == o7.code && o.Sw == o7.Sw && o.Skw == o7.Skw && o.pad == 0);
           CHECK(std::memcmp(o.row, o7.row, 6 * sizeof(double)) == 0 && o.row[12] == o7.row[6]);
           bool any = false;
@@ -141,15 +166,15 @@ static void check_windows() {
   for (int c : {0, 1, 3, 4, 5}) CHECK(codes_seen[c] > 0);
   std::printf("windows: codes 0..5 seen %d %d %d %d %d %d\n", codes_seen[0], codes_seen[1], codes_seen[2], codes_seen[3],
               codes_seen[4], codes_seen[5]);
-  CHECK(cal::tri(0, 0) == 0 && cal::tri(0, 12) == 12 && cal::tri(1, 1) == 13 && cal::tri(12, 12) == 90);
+  CHECK(xc::tri(0, 0) == 0 && xc::tri(0, 12) == 12 && xc::tri(1, 1) == 13 && xc::tri(12, 12) == 90);
   int n = 0;
   for (int a = 0; a < 13; a++)
-    for (int b = a; b < 13; b++) CHECK(cal::tri(a, b) == n++);
+    for (int b = a; b < 13; b++) CHECK(xc::tri(a, b) == n++);
 }
 
 static void random_acc(int N, int C, uint32_t fm, int zero_pose_col, int zero_ext_col, std::vector<double>& acc,
                        std::vector<int32_t>& cnt) {
-  acc.assign((size_t)N * C * cal::kAcc, 0.0);
+  acc.assign((size_t)N * C * xc::kAcc, 0.0);
   cnt.assign((size_t)N * C, 40);
   for (int r = 0; r < N; r++)
     for (int c = 0; c < C; c++)
@@ -160,7 +185,7 @@ static void random_acc(int N, int C, uint32_t fm, int zero_pose_col, int zero_ex
           for (int e = 6; e < 12; e++) row[e] = 0.0;
         if (zero_pose_col >= 0 && r == N - 1) row[zero_pose_col] = 0.0;
         if (zero_ext_col >= 0) row[6 + zero_ext_col] = 0.0;
-        cal::accumulate_row(row, acc.data() + (size_t)cal::kAcc * (r * C + c));
+        xc::accumulate_row(row, acc.data() + (size_t)xc::kAcc * (r * C + c));
       }
 }
 
@@ -173,6 +198,8 @@ static void check_passes() {
     const uint32_t fm = shape == 2 ? 0xfeu : 0x2u;
     int fcam[8];
     const int F = cal::free_list(fm, C, fcam);
+    lc::Layout lay;
+    xc::layout(fm, 0u, C, lay);
     std::vector<double> acc, T0((size_t)16 * N), T;
     std::vector<int32_t> cnt;
     for (int r = 0; r < N; r++) std::memcpy(T0.data() + 16 * r, I4, sizeof(I4));
@@ -186,26 +213,26 @@ static void check_passes() {
     // a step: the full normal equations hold at (delta, eps)
     random_acc(N, C, fm, -1, -1, acc, cnt);
     fresh(R);
-    CHECK(!cal::end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 12, 0.0, T.data(), R, delta.data()));
-    CHECK(R.status == cal::kOk && R.iterations_run == 1 && R.n_obs[0] == 40 * N * C && R.n_obs_cam[0][C - 1] == 40 * N);
+    CHECK(!end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 12, 0.0, T.data(), R, delta.data()));
+    CHECK(R.status == lc::kOk && R.iterations_run == 1 && R.n_obs[0] == 40 * N * C && R.n_obs_cam[0][C - 1] == 40 * N);
     double worst = 0;
     for (int r = 0; r < N; r++)
       for (int i = 0; i < 6; i++) {  // A_r delta_r + E_r eps = -a_r
         double s = 0;
-        for (int j = 0; j < 6; j++) s += cal::view_A(acc.data() + (size_t)cal::kAcc * C * r, C, i, j, 0.0) * delta[6 * r + j];
+        for (int j = 0; j < 6; j++) s += xc::view_A(acc.data() + (size_t)xc::kAcc * C * r, C, i, j, 0.0) * delta[6 * r + j];
         for (int j = 0; j < 6 * F; j++)
-          s += cal::view_rhs(acc.data() + (size_t)cal::kAcc * C * r, C, fcam, 6 * F, i, j) * R.delta_cam[0][fcam[j / 6]][j % 6];
-        s += cal::view_rhs(acc.data() + (size_t)cal::kAcc * C * r, C, fcam, 6 * F, i, 6 * F);
+          s += xc::view_rhs(acc.data() + (size_t)xc::kAcc * C * r, C, lay, i, j) * R.delta_cam[0][fcam[j / 6]][j % 6];
+        s += xc::view_rhs(acc.data() + (size_t)xc::kAcc * C * r, C, lay, i, 6 * F);
         worst = std::fmax(worst, std::fabs(s));
       }
     for (int f = 0; f < F; f++)
       for (int i = 0; i < 6; i++) {  // sum_r E_rf^T delta_r + B_f eps_f = -b_f
         double s = 0;
         for (int r = 0; r < N; r++) {
-          const double* a = acc.data() + (size_t)cal::kAcc * (r * C + fcam[f]);
-          for (int k = 0; k < 6; k++) s += a[cal::tri(k, 6 + i)] * delta[6 * r + k];
-          for (int j = 0; j < 6; j++) s += a[i <= j ? cal::tri(6 + i, 6 + j) : cal::tri(6 + j, 6 + i)] * R.delta_cam[0][fcam[f]][j];
-          s += a[cal::tri(6 + i, 12)];
+          const double* a = acc.data() + (size_t)xc::kAcc * (r * C + fcam[f]);
+          for (int k = 0; k < 6; k++) s += a[xc::tri(k, 6 + i)] * delta[6 * r + k];
+          for (int j = 0; j < 6; j++) s += a[i <= j ? xc::tri(6 + i, 6 + j) : xc::tri(6 + j, 6 + i)] * R.delta_cam[0][fcam[f]][j];
+          s += a[xc::tri(6 + i, 12)];
         }
         worst = std::fmax(worst, std::fabs(s));
       }
@@ -215,7 +242,7 @@ static void check_passes() {
       if (!(fm >> c & 1)) CHECK(std::memcmp(R.T_base_cam[c], I4, sizeof(I4)) == 0);
     // the gate and the covariance on the same accumulators: positive diagonals, symmetric, zeros for held cameras
     R.iterations_run = 0;
-    cal::conclude(acc.data(), cnt.data(), N, C, fm, 12, 12, 0.0, R);
+    conclude(acc.data(), cnt.data(), N, C, fm, 12, 12, 0.0, R);
     CHECK(R.calibrated == 1);
     for (int c = 0; c < 8; c++)
       for (int i = 0; i < 6; i++) {
@@ -223,44 +250,44 @@ static void check_passes() {
         CHECK(fr ? R.covariance[c][7 * i] > 0 : R.covariance[c][7 * i] == 0.0);
         for (int j = 0; j < 6; j++) CHECK(R.covariance[c][6 * i + j] == R.covariance[c][6 * j + i]);
       }
-    cal::conclude(acc.data(), cnt.data(), N, C, fm, 12, 12, 1e-12, R);  // a gate no rms passes
+    conclude(acc.data(), cnt.data(), N, C, fm, 12, 12, 1e-12, R);  // a gate no rms passes
     CHECK(R.calibrated == 0 && R.covariance[1][0] == 0.0);
     // the final pass solves nothing, whatever the system
     fresh(R);
-    CHECK(cal::end_pass(acc.data(), cnt.data(), N, C, fm, 4, 4, 12, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == cal::kOk && R.n_obs[4] == 40 * N * C && T == T0);
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, 4, 4, 12, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kOk && R.n_obs[4] == 40 * N * C && T == T0);
     // starved: a view below min_obs, then a free camera below min_obs_cam
     fresh(R);
-    CHECK(cal::end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 40 * C + 1, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == cal::kStarved && R.iterations_run == 0 && T == T0);
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 40 * C + 1, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kStarved && R.iterations_run == 0 && T == T0);
     fresh(R);
-    CHECK(cal::end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 40 * N + 1, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == cal::kStarved && R.iterations_run == 0 && std::memcmp(R.T_base_cam[1], I4, sizeof(I4)) == 0);
-    cal::conclude(acc.data(), cnt.data(), N, C, fm, 12, 40 * N + 1, 0.0, R);
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 40 * N + 1, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kStarved && R.iterations_run == 0 && std::memcmp(R.T_base_cam[1], I4, sizeof(I4)) == 0);
+    conclude(acc.data(), cnt.data(), N, C, fm, 12, 40 * N + 1, 0.0, R);
     CHECK(R.calibrated == 0);
     // singular A_r: the last view sees nothing of one pose direction
     random_acc(N, C, fm, 2, -1, acc, cnt);
     fresh(R);
-    CHECK(cal::end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == cal::kSingular && R.iterations_run == 0 && T == T0);
-    CHECK(!cal::end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 12, 1e-3, T.data(), (fresh(R), R), nullptr));  // damped
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kSingular && R.iterations_run == 0 && T == T0);
+    CHECK(!end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 12, 1e-3, T.data(), (fresh(R), R), nullptr));  // damped
     // singular S: A_r fine, one extrinsic direction unseen by every row
     random_acc(N, C, fm, -1, 3, acc, cnt);
     fresh(R);
-    CHECK(cal::end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == cal::kSingular && R.iterations_run == 0 && T == T0);
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kSingular && R.iterations_run == 0 && T == T0);
     for (int c = 0; c < C; c++) CHECK(std::memcmp(R.T_base_cam[c], I4, sizeof(I4)) == 0);
-    R.status = cal::kOk;
-    cal::conclude(acc.data(), cnt.data(), N, C, fm, 12, 12, 0.0, R);
+    R.status = lc::kOk;
+    conclude(acc.data(), cnt.data(), N, C, fm, 12, 12, 0.0, R);
     CHECK(R.calibrated == 0 && R.covariance[1][0] == 0.0);
   }
   // no row at all: rms is 0, not 0 / 0
-  std::vector<double> acc((size_t)2 * cal::kAcc, 0.0), T(I4, I4 + 16);
+  std::vector<double> acc((size_t)2 * xc::kAcc, 0.0), T(I4, I4 + 16);
   std::vector<int32_t> cnt(2, 0);
   mantis_calib_result R{};
-  CHECK(cal::end_pass(acc.data(), cnt.data(), 1, 2, 2u, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
-  CHECK(R.status == cal::kStarved && R.rms[0] == 0.0 && R.n_obs[0] == 0);
-  cal::conclude(acc.data(), cnt.data(), 1, 2, 2u, 12, 12, 0.0, R);
+  CHECK(end_pass(acc.data(), cnt.data(), 1, 2, 2u, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
+  CHECK(R.status == lc::kStarved && R.rms[0] == 0.0 && R.n_obs[0] == 0);
+  conclude(acc.data(), cnt.data(), 1, 2, 2u, 12, 12, 0.0, R);
   CHECK(R.calibrated == 0 && R.rms_cam[1] == 0.0);
 }
 
@@ -314,15 +341,15 @@ static void check_seq() {
     p.landmark_pitch = pitch * 0.5;
     mantis_calib_params cp{(int32_t)sizeof(mantis_calib_params), (int32_t)fm, 12, 0};
     mantis_calib_result res;
-    std::vector<cal::Slot> slots((size_t)N * C * nc);
-    cal::calib_seq(T0.data(), E_nom.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, cp,
+    std::vector<xc::Slot> slots((size_t)N * C * nc);
+    calib_seq(T0.data(), E_nom.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, cp,
                    T_out.data(), res, slots.data());
     const double e0 = ext_dist(E_nom.data() + 16 * moved, E_true.data() + 16 * moved);
     const double e1 = ext_dist(res.T_base_cam[moved], E_true.data() + 16 * moved);
     std::printf("seq N=%d C=%d R=%d: status %d calibrated %d runs %d n_obs %d..%d  camera %d: %.5f -> %.5f m  rms %.3g -> %.3g\n",
                 N, C, Rw, res.status, res.calibrated, res.iterations_run, res.n_obs[0], res.n_obs[res.iterations_run],
                 moved, e0, e1, res.rms[0], res.rms[res.iterations_run]);
-    CHECK(res.status == cal::kOk && res.iterations_run == 5 && res.n_cand == nc && res.n_rigs == N && res.n_cams == C);
+    CHECK(res.status == lc::kOk && res.iterations_run == 5 && res.n_cand == nc && res.n_rigs == N && res.n_cams == C);
     CHECK(res.calibrated == 1 && e1 < e0 && res.rms[5] < res.rms[0]);
     CHECK(std::memcmp(res.T_base_cam[0], E_nom.data(), 16 * sizeof(double)) == 0);
     for (int c = C; c < 8; c++)
@@ -332,14 +359,14 @@ static void check_seq() {
         for (int e = 0; e < 13; e++) CHECK(slots[k].row[e] == 0.0);
     // I = 0: every pose and extrinsic comes back bit for bit
     p.iterations = 0;
-    cal::calib_seq(T0.data(), E_nom.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, cp,
+    calib_seq(T0.data(), E_nom.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, cp,
                    T_out.data(), res, nullptr);
     CHECK(std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0 && res.iterations_run == 0);
     CHECK(std::memcmp(res.T_base_cam, E_nom.data(), sizeof(double) * 16 * C) == 0);
     // R = 1: three samples; whatever the rule says, finite
     p.iterations = 3;
     p.half_window = 1;
-    cal::calib_seq(T_true.data(), E_true.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p,
+    calib_seq(T_true.data(), E_true.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p,
                    cp, T_out.data(), res, nullptr);
     for (size_t e = 0; e < T_out.size(); e++) CHECK(std::isfinite(T_out[e]));
     // starved: the last view black (a view's gate), then the displaced free camera black in every view (a camera's)
@@ -347,19 +374,19 @@ static void check_seq() {
     std::vector<uint8_t> black((size_t)W * H * 3, 0);
     std::vector<const uint8_t*> fb = frames;
     for (int c = 0; c < C; c++) fb[(N - 1) * C + c] = black.data();
-    cal::calib_seq(T0.data(), E_nom.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, cp,
+    calib_seq(T0.data(), E_nom.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, cp,
                    T_out.data(), res, nullptr);
-    CHECK(res.status == cal::kStarved && res.calibrated == 0 && std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0);
+    CHECK(res.status == lc::kStarved && res.calibrated == 0 && std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0);
     fb = frames;
     for (int r = 0; r < N; r++) fb[r * C + moved] = black.data();
-    cal::calib_seq(T0.data(), E_nom.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, cp,
+    calib_seq(T0.data(), E_nom.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, cp,
                    T_out.data(), res, nullptr);
-    CHECK(res.status == cal::kStarved && res.n_obs_cam[0][moved] == 0 && res.n_obs[0] > 12 * N);
+    CHECK(res.status == lc::kStarved && res.n_obs_cam[0][moved] == 0 && res.n_obs[0] > 12 * N);
     CHECK(std::memcmp(res.T_base_cam, E_nom.data(), sizeof(double) * 16 * C) == 0);
     // no candidates at all
-    cal::calib_seq(T0.data(), E_nom.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), 0, p, cp,
+    calib_seq(T0.data(), E_nom.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), 0, p, cp,
                    T_out.data(), res, nullptr);
-    CHECK(res.status == cal::kStarved && res.rms[0] == 0.0);
+    CHECK(res.status == lc::kStarved && res.rms[0] == 0.0);
   }
 }
 

@@ -1,5 +1,5 @@
 // Stand-alone check of the intrinsic calibration's rules (mantis_amd/csrc/
-// mk_icalib.h: one observation with its window over the frame edges and the
+// mk_linecal.h at the problem Int, mk_icalib.h: one observation with its window over the frame edges and the
 // intrinsics' columns, the end of a pass with both starved gates, both
 // singular exits and the diverged exit, the gate and the covariance, the
 // whole call for N = 1 and 3 views, C = 1 and 8 cameras with all free, R = 1,
@@ -15,11 +15,37 @@
 #include <cstring>
 #include <vector>
 
-#include "../mantis_amd/csrc/mk_icalib.h"
+#include "../mantis_amd/csrc/mk_linecal.h"
 
 namespace rf = mk::refine;
 namespace cal = mk::calib;
 namespace ic = mk::icalib;
+namespace lc = mk::linecal;
+using xi = lc::Int;  // the shared rules at the intrinsic calibration's problem
+
+// the shared rules on the intrinsic calibration's public struct
+static bool end_pass(const double* acc, const int32_t* cnt, int N, int C, uint32_t fm, uint32_t pm, int pass, int I,
+                     int32_t min_obs, int32_t min_obs_cam, double lambda, double* T, mantis_icalib_result& R,
+                     double* delta) {
+  return lc::with_state(R, [&](mantis_rcalib_result& w) {
+    return xi::end_pass(acc, cnt, N, C, 0u, fm, pm, pass, I, min_obs, min_obs_cam, lambda, T, w, delta);
+  });
+}
+static void conclude(const double* acc, const int32_t* cnt, int N, int C, uint32_t fm, uint32_t pm, int32_t min_obs,
+                     int32_t min_obs_cam, double max_rms, mantis_icalib_result& R) {
+  lc::with_state(R, [&](mantis_rcalib_result& w) {
+    xi::conclude(acc, cnt, N, C, 0u, fm, pm, min_obs, min_obs_cam, max_rms, w);
+  });
+}
+static void icalib_seq(const double* T_in, const double* Tbc, const mk::Cam* cams, const uint8_t* const* frames, int N,
+                       int C, int W, int H, const double* X, int nw, int nr, const int32_t* cand, int n_cand,
+                       const mantis_refine_params& p, const mantis_icalib_params& ip, double* T_out,
+                       mantis_icalib_result& R, xi::Slot* slots) {
+  mantis_rcalib_result w;
+  xi::seq(T_in, Tbc, cams, frames, N, C, W, H, X, nw, nr, cand, n_cand, p, 0u, (uint32_t)ip.free_cams,
+          (uint32_t)ip.param_mask, ip.min_obs_cam, T_out, w, slots);
+  lc::narrow(w, R);
+}
 
 static int g_fail = 0;
 static bool g_verbose = false;
@@ -119,9 +145,9 @@ static void check_windows() {
         rf::observe(Rt, t, gc, cam, img.data(), W, H, X, trial & 1, tg, win, o7, nullptr);
         const uint32_t mask = trial % 5 == 0 ? 0x5Au : 0xFFu;
         for (int fr = 0; fr < 2; fr++) {
-          ic::Slot o;
+          xi::Slot o;
           int tie;
-          ic::observe(Rt, t, gc, cam, img.data(), W, H, X, trial & 1, tg, win, fr != 0, mask, o, &tie);
+          xi::observe(Rt, t, gc, cam, img.data(), W, H, X, trial & 1, tg, win, false, fr != 0, mask, o, &tie);
           CHECK(o.code == o7.code && o.Sw == o7.Sw && o.Skw == o7.Skw && o.pad == 0);
           CHECK(std::memcmp(o.row, o7.row, 6 * sizeof(double)) == 0 && o.row[14] == o7.row[6]);
           bool any = false;
@@ -142,10 +168,10 @@ static void check_windows() {
   if (g_verbose)
     std::printf("windows: codes 0..5 seen %d %d %d %d %d %d\n", codes_seen[0], codes_seen[1], codes_seen[2],
                 codes_seen[3], codes_seen[4], codes_seen[5]);
-  CHECK(ic::tri(0, 0) == 0 && ic::tri(0, 14) == 14 && ic::tri(1, 1) == 15 && ic::tri(14, 14) == 119);
+  CHECK(xi::tri(0, 0) == 0 && xi::tri(0, 14) == 14 && xi::tri(1, 1) == 15 && xi::tri(14, 14) == 119);
   int n = 0;
   for (int a = 0; a < 15; a++)
-    for (int b = a; b < 15; b++) CHECK(ic::tri(a, b) == n++);
+    for (int b = a; b < 15; b++) CHECK(xi::tri(a, b) == n++);
   // on the axis: G = I, c = 1, the k columns zero
   const mk::Cam cam{60.0, 61.0, 20.0, 16.0, {0.003, -0.01, 0.005, -0.002}};
   const double m0[2] = {0.0, 0.0}, nh[2] = {0.6, -0.8};
@@ -161,7 +187,7 @@ static void check_windows() {
 
 static void random_acc(int N, int C, uint32_t fm, uint32_t pm, int zero_pose_col, int zero_int_col, double r_scale,
                        std::vector<double>& acc, std::vector<int32_t>& cnt) {
-  acc.assign((size_t)N * C * ic::kAcc, 0.0);
+  acc.assign((size_t)N * C * xi::kAcc, 0.0);
   cnt.assign((size_t)N * C, 60);
   for (int r = 0; r < N; r++)
     for (int c = 0; c < C; c++)
@@ -173,7 +199,7 @@ static void random_acc(int N, int C, uint32_t fm, uint32_t pm, int zero_pose_col
           if (!(fm >> c & 1) || !(pm >> e & 1)) row[6 + e] = 0.0;
         if (zero_pose_col >= 0 && r == N - 1) row[zero_pose_col] = 0.0;
         if (zero_int_col >= 0) row[6 + zero_int_col] = 0.0;
-        ic::accumulate_row(row, acc.data() + (size_t)ic::kAcc * (r * C + c));
+        xi::accumulate_row(row, acc.data() + (size_t)xi::kAcc * (r * C + c));
       }
 }
 
@@ -188,6 +214,8 @@ static void check_passes() {
     const uint32_t pm = shape == 3 ? 0x3Fu : 0xFFu;
     int fcam[8], np = 0;
     const int F = cal::free_list(fm, C, fcam), nS = 8 * F;
+    lc::Layout lay;
+    xi::layout(0u, fm, C, lay);
     for (int e = 0; e < 8; e++) np += (int)(pm >> e & 1u);
     std::vector<double> acc, T0((size_t)16 * N), T;
     std::vector<int32_t> cnt;
@@ -210,16 +238,16 @@ static void check_passes() {
     // a step: the full normal equations hold at (delta, eps)
     random_acc(N, C, fm, pm, -1, -1, 0.01, acc, cnt);
     fresh(R);
-    CHECK(!ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 0.0, T.data(), R, delta.data()));
-    CHECK(R.status == ic::kOk && R.iterations_run == 1 && R.n_obs[0] == 60 * N * C && R.n_obs_cam[0][C - 1] == 60 * N);
+    CHECK(!end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 0.0, T.data(), R, delta.data()));
+    CHECK(R.status == lc::kOk && R.iterations_run == 1 && R.n_obs[0] == 60 * N * C && R.n_obs_cam[0][C - 1] == 60 * N);
     double worst = 0;
     for (int r = 0; r < N; r++)
       for (int i = 0; i < 6; i++) {  // A_r delta_r + E_r eps = -a_r
-        const double* av = acc.data() + (size_t)ic::kAcc * C * r;
+        const double* av = acc.data() + (size_t)xi::kAcc * C * r;
         double s = 0;
-        for (int j = 0; j < 6; j++) s += ic::view_A(av, C, i, j, 0.0) * delta[6 * r + j];
-        for (int j = 0; j < nS; j++) s += ic::view_rhs(av, C, fcam, nS, i, j) * R.delta_cam[0][fcam[j / 8]][j % 8];
-        s += ic::view_rhs(av, C, fcam, nS, i, nS);
+        for (int j = 0; j < 6; j++) s += xi::view_A(av, C, i, j, 0.0) * delta[6 * r + j];
+        for (int j = 0; j < nS; j++) s += xi::view_rhs(av, C, lay, i, j) * R.delta_cam[0][fcam[j / 8]][j % 8];
+        s += xi::view_rhs(av, C, lay, i, nS);
         worst = std::fmax(worst, std::fabs(s));
       }
     for (int f = 0; f < F; f++)
@@ -230,10 +258,10 @@ static void check_passes() {
         }
         double s = 0;
         for (int r = 0; r < N; r++) {
-          const double* a = acc.data() + (size_t)ic::kAcc * (r * C + fcam[f]);
-          for (int k = 0; k < 6; k++) s += a[ic::tri(k, 6 + i)] * delta[6 * r + k];
-          for (int j = 0; j < 8; j++) s += a[ic::tri_sym(6 + i, 6 + j)] * R.delta_cam[0][fcam[f]][j];
-          s += a[ic::tri(6 + i, 14)];
+          const double* a = acc.data() + (size_t)xi::kAcc * (r * C + fcam[f]);
+          for (int k = 0; k < 6; k++) s += a[xi::tri(k, 6 + i)] * delta[6 * r + k];
+          for (int j = 0; j < 8; j++) s += a[xi::tri_sym(6 + i, 6 + j)] * R.delta_cam[0][fcam[f]][j];
+          s += a[xi::tri(6 + i, 14)];
         }
         worst = std::fmax(worst, std::fabs(s));
       }
@@ -251,8 +279,8 @@ static void check_passes() {
     // the gate and the covariance on the same accumulators: positive diagonals for the free parameters,
     // symmetric, zeros for held cameras and held parameters
     fresh(R);
-    (void)ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 0, 12, 12, 0.0, T.data(), R, nullptr);  // the figures
-    ic::conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 12, 0.0, R);
+    (void)end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 0, 12, 12, 0.0, T.data(), R, nullptr);  // the figures
+    conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 12, 0.0, R);
     CHECK(R.calibrated == 1);
     for (int c = 0; c < 8; c++)
       for (int i = 0; i < 8; i++) {
@@ -263,47 +291,47 @@ static void check_passes() {
           if (!fr) CHECK(R.covariance[c][8 * i + j] == 0.0);
         }
       }
-    ic::conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 12, 1e-12, R);  // a gate no rms passes
+    conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 12, 1e-12, R);  // a gate no rms passes
     CHECK(R.calibrated == 0 && R.covariance[C - 1][0] == 0.0);
     // the final pass solves nothing, whatever the system
     fresh(R);
-    CHECK(ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 4, 4, 12, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == ic::kOk && R.n_obs[4] == 60 * N * C && T == T0 && same_kd(R));
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, pm, 4, 4, 12, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kOk && R.n_obs[4] == 60 * N * C && T == T0 && same_kd(R));
     // starved: a view below min_obs, then a free camera below min_obs_cam
     fresh(R);
-    CHECK(ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 60 * C + 1, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == ic::kStarved && R.iterations_run == 0 && T == T0 && same_kd(R));
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 60 * C + 1, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kStarved && R.iterations_run == 0 && T == T0 && same_kd(R));
     fresh(R);
-    CHECK(ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 60 * N + 1, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == ic::kStarved && R.iterations_run == 0 && same_kd(R));
-    ic::conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 60 * N + 1, 0.0, R);
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 60 * N + 1, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kStarved && R.iterations_run == 0 && same_kd(R));
+    conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 60 * N + 1, 0.0, R);
     CHECK(R.calibrated == 0);
     // singular A_r: the last view sees nothing of one pose direction
     random_acc(N, C, fm, pm, 2, -1, 0.01, acc, cnt);
     fresh(R);
-    CHECK(ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == ic::kSingular && R.iterations_run == 0 && T == T0 && same_kd(R));
-    CHECK(!ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 1e-3, T.data(), (fresh(R), R), nullptr));  // damped
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kSingular && R.iterations_run == 0 && T == T0 && same_kd(R));
+    CHECK(!end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 1e-3, T.data(), (fresh(R), R), nullptr));  // damped
     // singular S: A_r fine, one free intrinsic unseen by every row
     random_acc(N, C, fm, pm, -1, 3, 0.01, acc, cnt);
     fresh(R);
-    CHECK(ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == ic::kSingular && R.iterations_run == 0 && T == T0 && same_kd(R));
-    R.status = ic::kOk;
-    ic::conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 12, 0.0, R);
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kSingular && R.iterations_run == 0 && T == T0 && same_kd(R));
+    R.status = lc::kOk;
+    conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 12, 0.0, R);
     CHECK(R.calibrated == 0 && R.covariance[C - 1][0] == 0.0);
     // ... and the same accumulators with that parameter held: its diagonal is 1, the step is taken
     fresh(R);
-    CHECK(!ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm & ~8u, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == ic::kOk && R.K[C - 1][3] == K0[3]);
+    CHECK(!end_pass(acc.data(), cnt.data(), N, C, fm, pm & ~8u, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
+    CHECK(R.status == lc::kOk && R.K[C - 1][3] == K0[3]);
     // diverged: residuals a thousand times the Jacobian's entries push some fx (1 + eps) or fy below zero
     random_acc(N, C, fm, pm, -1, -1, 1e3, acc, cnt);
     fresh(R);
-    CHECK(ic::end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 0.0, T.data(), R, delta.data()));
-    CHECK(R.status == ic::kDiverged && R.iterations_run == 0 && T == T0 && same_kd(R));
+    CHECK(end_pass(acc.data(), cnt.data(), N, C, fm, pm, 0, 4, 12, 12, 0.0, T.data(), R, delta.data()));
+    CHECK(R.status == lc::kDiverged && R.iterations_run == 0 && T == T0 && same_kd(R));
     for (int c = 0; c < 8; c++)
       for (int e = 0; e < 8; e++) CHECK(R.delta_cam[0][c][e] == 0.0);
-    ic::conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 12, 0.0, R);
+    conclude(acc.data(), cnt.data(), N, C, fm, pm, 12, 12, 0.0, R);
     CHECK(R.calibrated == 0);
   }
   // param_update on its own: the order of the scaling, the held bits, the three ways to diverge
@@ -316,12 +344,12 @@ static void check_passes() {
   CHECK(!ic::param_update(th, e2, 0xFFu, out) && !ic::param_update(th, e3, 0xFFu, out) && !ic::param_update(th, e4, 0xFFu, out));
   CHECK(ic::param_update(th, e3, 0xDFu, out) && out[5] == 2);
   // no row at all: rms is 0, not 0 / 0
-  std::vector<double> acc((size_t)2 * ic::kAcc, 0.0), T(I4, I4 + 16);
+  std::vector<double> acc((size_t)2 * xi::kAcc, 0.0), T(I4, I4 + 16);
   std::vector<int32_t> cnt(2, 0);
   mantis_icalib_result R{};
-  CHECK(ic::end_pass(acc.data(), cnt.data(), 1, 2, 3u, 0xFFu, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
-  CHECK(R.status == ic::kStarved && R.rms[0] == 0.0 && R.n_obs[0] == 0);
-  ic::conclude(acc.data(), cnt.data(), 1, 2, 3u, 0xFFu, 12, 12, 0.0, R);
+  CHECK(end_pass(acc.data(), cnt.data(), 1, 2, 3u, 0xFFu, 0, 4, 12, 12, 0.0, T.data(), R, nullptr));
+  CHECK(R.status == lc::kStarved && R.rms[0] == 0.0 && R.n_obs[0] == 0);
+  conclude(acc.data(), cnt.data(), 1, 2, 3u, 0xFFu, 12, 12, 0.0, R);
   CHECK(R.calibrated == 0 && R.rms_cam[1] == 0.0);
 }
 
@@ -395,8 +423,8 @@ static void check_seq() {
     p.landmark_pitch = pitch * 0.5;
     mantis_icalib_params ip{(int32_t)sizeof(mantis_icalib_params), (int32_t)fm, (int32_t)pm, 12};
     mantis_icalib_result res;
-    std::vector<ic::Slot> slots((size_t)N * C * nc);
-    ic::icalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, ip,
+    std::vector<xi::Slot> slots((size_t)N * C * nc);
+    icalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, ip,
                    T_out.data(), res, slots.data());
     double g0 = 0, g1 = 0;
     for (int c = 0; c < C; c++) {
@@ -407,7 +435,7 @@ static void check_seq() {
       std::printf("seq N=%d C=%d R=%d mask=%#x: status %d calibrated %d runs %d n_obs %d..%d  worst gap %.3f -> %.3f px  rms %.3g -> %.3g\n",
                   N, C, Rw, pm, res.status, res.calibrated, res.iterations_run, res.n_obs[0],
                   res.n_obs[res.iterations_run], g0, g1, res.rms[0], res.rms[res.iterations_run]);
-    CHECK(res.status == ic::kOk && res.iterations_run == 5 && res.n_cand == nc && res.n_rigs == N && res.n_cams == C);
+    CHECK(res.status == lc::kOk && res.iterations_run == 5 && res.n_cand == nc && res.n_rigs == N && res.n_cams == C);
     CHECK(res.free_cams == (int32_t)fm && res.param_mask == (int32_t)pm);
     CHECK(res.calibrated == 1 && g1 < g0 && res.rms[5] < res.rms[0]);
     for (int c = 0; c < C; c++)
@@ -420,7 +448,7 @@ static void check_seq() {
         for (int e = 0; e < 15; e++) CHECK(slots[k].row[e] == 0.0);
     // I = 0: every pose and intrinsic comes back bit for bit
     p.iterations = 0;
-    ic::icalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, ip,
+    icalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, ip,
                    T_out.data(), res, nullptr);
     CHECK(std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0 && res.iterations_run == 0);
     for (int c = 0; c < C; c++) {
@@ -431,7 +459,7 @@ static void check_seq() {
     // R = 1: three samples; whatever the rule says, finite
     p.iterations = 3;
     p.half_window = 1;
-    ic::icalib_seq(T_true.data(), E.data(), truth.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p,
+    icalib_seq(T_true.data(), E.data(), truth.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p,
                    ip, T_out.data(), res, nullptr);
     for (size_t e = 0; e < T_out.size(); e++) CHECK(std::isfinite(T_out[e]));
     for (int c = 0; c < C; c++)
@@ -441,21 +469,21 @@ static void check_seq() {
     std::vector<uint8_t> black((size_t)W * H * 3, 0);
     std::vector<const uint8_t*> fb = frames;
     for (int c = 0; c < C; c++) fb[(N - 1) * C + c] = black.data();
-    ic::icalib_seq(T0.data(), E.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, ip,
+    icalib_seq(T0.data(), E.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, ip,
                    T_out.data(), res, nullptr);
-    CHECK(res.status == ic::kStarved && res.calibrated == 0 && std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0);
+    CHECK(res.status == lc::kStarved && res.calibrated == 0 && std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0);
     if (C > 1) {
       fb = frames;
       for (int r = 0; r < N; r++) fb[r * C + C - 1] = black.data();
-      ic::icalib_seq(T0.data(), E.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, ip,
+      icalib_seq(T0.data(), E.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, ip,
                      T_out.data(), res, nullptr);
-      CHECK(res.status == ic::kStarved && res.n_obs_cam[0][C - 1] == 0 && res.n_obs[0] > 12 * N);
+      CHECK(res.status == lc::kStarved && res.n_obs_cam[0][C - 1] == 0 && res.n_obs[0] > 12 * N);
       CHECK(res.K[C - 1][0] == nominal.fx);
     }
     // no candidates at all
-    ic::icalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), 0, p, ip,
+    icalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), 0, p, ip,
                    T_out.data(), res, nullptr);
-    CHECK(res.status == ic::kStarved && res.rms[0] == 0.0);
+    CHECK(res.status == lc::kStarved && res.rms[0] == 0.0);
   }
 }
 

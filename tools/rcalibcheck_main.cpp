@@ -1,6 +1,7 @@
 // Stand-alone check of the rig calibration's rules (mantis_amd/csrc/
-// mk_rcalib.h: one observation with J_ext and J_int against central
-// differences and beside the two single calibrations' slots, the end of a
+// mk_linecal.h at the problem Rig: one observation with J_ext and J_int
+// against central differences and beside the slots of the problems Ext and
+// Int (the two single calibrations' instantiations), the end of a
 // pass -- the three-block reduction (poses | extrinsics | intrinsics) against
 // a dense solve of the full normal system, both starved gates, both singular
 // exits and the diverged exit --, the gate and the covariances, and the whole
@@ -16,12 +17,21 @@
 #include <cstring>
 #include <vector>
 
-#include "../mantis_amd/csrc/mk_rcalib.h"
+#include "../mantis_amd/csrc/mk_linecal.h"
 
 namespace rf = mk::refine;
 namespace cal = mk::calib;
 namespace ic = mk::icalib;
-namespace rc = mk::rcalib;
+namespace lc = mk::linecal;
+using rc = lc::Rig;  // the shared rules at the rig calibration's problem
+
+static void rcalib_seq(const double* T_in, const double* Tbc, const mk::Cam* cams, const uint8_t* const* frames, int N,
+                       int C, int W, int H, const double* X, int nw, int nr, const int32_t* cand, int n_cand,
+                       const mantis_refine_params& p, const mantis_rcalib_params& rp, double* T_out,
+                       mantis_rcalib_result& R, rc::Slot* slots) {
+  rc::seq(T_in, Tbc, cams, frames, N, C, W, H, X, nw, nr, cand, n_cand, p, (uint32_t)rp.free_ext, (uint32_t)rp.free_int,
+          (uint32_t)rp.param_mask, rp.min_obs_cam, T_out, R, slots);
+}
 
 static int g_fail = 0;
 static bool g_verbose = false;
@@ -152,10 +162,10 @@ static void check_rows() {
         double Rt[9], t[3];
         rf::pose_parts(T, Rt, t);
         const uint32_t mask = trial % 5 == 0 ? 0x5Au : 0xFFu;
-        cal::Slot oc;
-        ic::Slot oi;
-        cal::observe(Rt, t, gc, cam, img.data(), W, H, X, axis, tg, win, true, oc, nullptr);
-        ic::observe(Rt, t, gc, cam, img.data(), W, H, X, axis, tg, win, true, mask, oi, nullptr);
+        lc::Ext::Slot oc;
+        lc::Int::Slot oi;
+        lc::Ext::observe(Rt, t, gc, cam, img.data(), W, H, X, axis, tg, win, true, false, 0u, oc, nullptr);
+        lc::Int::observe(Rt, t, gc, cam, img.data(), W, H, X, axis, tg, win, false, true, mask, oi, nullptr);
         for (int fe = 0; fe < 2; fe++)
           for (int fi = 0; fi < 2; fi++) {
             rc::Slot o;
@@ -227,7 +237,7 @@ static void check_rows() {
   for (int a = 0; a < rc::kRow; a++)
     for (int b = a; b < rc::kRow; b++) CHECK(rc::tri(a, b) == n++);
   CHECK(n == rc::kAcc && rc::tri(20, 20) == 230 && sizeof(rc::Slot) == 184 && rc::kMaxS == 106);
-  rc::Layout l;
+  lc::Layout l;
   rc::layout(0xFEu, 0xFFu, 8, l);
   int cam, col;
   CHECK(l.Fe == 7 && l.Fi == 8 && l.nS == 106);
@@ -298,7 +308,7 @@ static void check_passes() {
     const uint32_t fi = shape == 0 ? 0x3u : shape == 1 ? 0x1u : shape == 2 ? 0x4u : 0xFFu;
     const uint32_t pm = shape == 4 ? 0x3Fu : 0xFFu;
     const double lam = shape == 3 ? 1e-3 : 0.0;
-    rc::Layout l;
+    lc::Layout l;
     rc::layout(fe, fi, C, l);
     const int nS = l.nS, nF = 6 * N + nS;
     int np = 0;
@@ -338,7 +348,7 @@ static void check_passes() {
     random_acc(N, C, fe, fi, pm, -1, -1, 0.01, acc, cnt);
     fresh(R);
     CHECK(!rc::end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm, 0, 4, 12, 14, lam, T.data(), R, delta.data()));
-    CHECK(R.status == rc::kOk && R.iterations_run == 1 && R.n_obs[0] == 60 * N * C && R.n_obs_cam[0][C - 1] == 60 * N);
+    CHECK(R.status == lc::kOk && R.iterations_run == 1 && R.n_obs[0] == 60 * N * C && R.n_obs_cam[0][C - 1] == 60 * N);
     std::vector<double> Hm((size_t)nF * nF, 0.0), g((size_t)nF, 0.0);
     for (int r = 0; r < N; r++)
       for (int c = 0; c < C; c++) {
@@ -418,39 +428,39 @@ static void check_passes() {
     // the final pass solves nothing, whatever the system
     fresh(R);
     CHECK(rc::end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm, 4, 4, 12, 14, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == rc::kOk && R.n_obs[4] == 60 * N * C && T == T0 && same_rig(R));
+    CHECK(R.status == lc::kOk && R.n_obs[4] == 60 * N * C && T == T0 && same_rig(R));
     // starved: a view below min_obs, then a camera free in either mask below min_obs_cam
     fresh(R);
     CHECK(rc::end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm, 0, 4, 60 * C + 1, 14, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == rc::kStarved && R.iterations_run == 0 && T == T0 && same_rig(R));
+    CHECK(R.status == lc::kStarved && R.iterations_run == 0 && T == T0 && same_rig(R));
     for (int c = 0; c < C; c++) {
       std::vector<int32_t> few = cnt;
       for (int r = 0; r < N; r++) few[r * C + c] = 4;  // 4 N < 14 rows of camera c, every view still above min_obs
       fresh(R);
       const bool fin = rc::end_pass(acc.data(), few.data(), N, C, fe, fi, pm, 0, 4, 12, 14, 0.0, T.data(), R, nullptr);
       const bool gated = ((fe | fi) >> c & 1u) != 0;
-      CHECK(fin == gated && (R.status == rc::kStarved) == gated);
+      CHECK(fin == gated && (R.status == lc::kStarved) == gated);
     }
     // singular A_r: the last view sees nothing of one pose direction
     random_acc(N, C, fe, fi, pm, 2, -1, 0.01, acc, cnt);
     fresh(R);
     CHECK(rc::end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm, 0, 4, 12, 14, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == rc::kSingular && R.iterations_run == 0 && T == T0 && same_rig(R) && no_steps(R));
+    CHECK(R.status == lc::kSingular && R.iterations_run == 0 && T == T0 && same_rig(R) && no_steps(R));
     CHECK(!rc::end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm, 0, 4, 12, 14, 1e-3, T.data(), (fresh(R), R), nullptr));  // damped
     // singular S: A_r fine, one extrinsic direction, then one free intrinsic, unseen by every row
     for (int zc : {8, 15}) {
       random_acc(N, C, fe, fi, pm, -1, zc, 0.01, acc, cnt);
       fresh(R);
       CHECK(rc::end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm, 0, 4, 12, 14, 0.0, T.data(), R, nullptr));
-      CHECK(R.status == rc::kSingular && R.iterations_run == 0 && T == T0 && same_rig(R) && no_steps(R));
-      R.status = rc::kOk;
+      CHECK(R.status == lc::kSingular && R.iterations_run == 0 && T == T0 && same_rig(R) && no_steps(R));
+      R.status = lc::kOk;
       rc::conclude(acc.data(), cnt.data(), N, C, fe, fi, pm, 12, 14, 0.0, R);
       CHECK(R.calibrated == 0 && R.cov_int[C - 1][0] == 0.0);
     }
     // ... and the same accumulators with that parameter held: its diagonal is 1, the step is taken
     fresh(R);
     CHECK(!rc::end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm & ~8u, 0, 4, 12, 14, 0.0, T.data(), R, nullptr));
-    CHECK(R.status == rc::kOk && R.K[C - 1][3] == K0[3]);
+    CHECK(R.status == lc::kOk && R.K[C - 1][3] == K0[3]);
     // diverged: residuals a thousand times the Jacobian's entries push some fx (1 + eps) or fy below zero. The
     // same rows with r negated negate eps, so of the two signs at least one drives camera fi[0]'s fx below zero.
     int diverged = 0;
@@ -460,7 +470,7 @@ static void check_passes() {
       random_acc(N, C, fe, fi, pm, -1, -1, sign * 1e3, acc, cnt);
       fresh(R);
       const bool fin = rc::end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm, 0, 4, 12, 14, 0.0, T.data(), R, delta.data());
-      CHECK(fin == (R.status == rc::kDiverged));
+      CHECK(fin == (R.status == lc::kDiverged));
       if (!fin) continue;
       diverged++;
       CHECK(R.iterations_run == 0 && T == T0 && same_rig(R) && no_steps(R));
@@ -474,7 +484,7 @@ static void check_passes() {
   std::vector<int32_t> cnt(2, 0);
   mantis_rcalib_result R{};
   CHECK(rc::end_pass(acc.data(), cnt.data(), 1, 2, 2u, 3u, 0xFFu, 0, 4, 12, 14, 0.0, T.data(), R, nullptr));
-  CHECK(R.status == rc::kStarved && R.rms[0] == 0.0 && R.n_obs[0] == 0);
+  CHECK(R.status == lc::kStarved && R.rms[0] == 0.0 && R.n_obs[0] == 0);
   rc::conclude(acc.data(), cnt.data(), 1, 2, 2u, 3u, 0xFFu, 12, 14, 0.0, R);
   CHECK(R.calibrated == 0 && R.rms_cam[1] == 0.0);
 }
@@ -568,7 +578,7 @@ static void check_seq() {
     mantis_rcalib_params rp{(int32_t)sizeof(mantis_rcalib_params), (int32_t)fe, (int32_t)fi, (int32_t)pm, 14, 0};
     mantis_rcalib_result res;
     std::vector<rc::Slot> slots((size_t)N * C * nc);
-    rc::rcalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, rp,
+    rcalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, rp,
                    T_out.data(), res, slots.data());
     double g0 = 0, g1 = 0, e0 = 0, e1 = 0;
     for (int c = 0; c < C; c++) {
@@ -582,7 +592,7 @@ static void check_seq() {
                   "%.2f -> %.2f mm  rms %.3g -> %.3g\n",
                   N, C, Rw, res.status, res.calibrated, res.iterations_run, res.n_obs[0], res.n_obs[res.iterations_run], g0,
                   g1, 1e3 * e0, 1e3 * e1, res.rms[0], res.rms[res.iterations_run]);
-    CHECK(res.status == rc::kOk && res.iterations_run == 6 && res.n_cand == nc && res.n_rigs == N && res.n_cams == C);
+    CHECK(res.status == lc::kOk && res.iterations_run == 6 && res.n_cand == nc && res.n_rigs == N && res.n_cams == C);
     CHECK(res.free_ext == (int32_t)fe && res.free_int == (int32_t)fi && res.param_mask == (int32_t)pm);
     CHECK(res.calibrated == 1 && g1 < g0 && e1 < e0 && res.rms[6] < res.rms[0]);
     CHECK(std::memcmp(res.T_base_cam[0], E.data(), 16 * sizeof(double)) == 0);  // the gauge
@@ -595,7 +605,7 @@ static void check_seq() {
         for (int e = 0; e < 21; e++) CHECK(slots[k].row[e] == 0.0);
     // I = 0: every pose, extrinsic and intrinsic comes back bit for bit
     p.iterations = 0;
-    rc::rcalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, rp,
+    rcalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, rp,
                    T_out.data(), res, nullptr);
     CHECK(std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0 && res.iterations_run == 0);
     for (int c = 0; c < C; c++) {
@@ -607,7 +617,7 @@ static void check_seq() {
     // R = 1: three samples; whatever the rule says, finite
     p.iterations = 3;
     p.half_window = 1;
-    rc::rcalib_seq(T_true.data(), Et.data(), truth.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p,
+    rcalib_seq(T_true.data(), Et.data(), truth.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p,
                    rp, T_out.data(), res, nullptr);
     for (size_t e = 0; e < T_out.size(); e++) CHECK(std::isfinite(T_out[e]));
     for (int c = 0; c < C; c++) {
@@ -619,19 +629,19 @@ static void check_seq() {
     std::vector<uint8_t> black((size_t)W * H * 3, 0);
     std::vector<const uint8_t*> fb = frames;
     for (int c = 0; c < C; c++) fb[(N - 1) * C + c] = black.data();
-    rc::rcalib_seq(T0.data(), E.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, rp,
+    rcalib_seq(T0.data(), E.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, rp,
                    T_out.data(), res, nullptr);
-    CHECK(res.status == rc::kStarved && res.calibrated == 0 && std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0);
+    CHECK(res.status == lc::kStarved && res.calibrated == 0 && std::memcmp(T_out.data(), T0.data(), sizeof(double) * 16 * N) == 0);
     fb = frames;
     for (int r = 0; r < N; r++) fb[r * C + C - 1] = black.data();
-    rc::rcalib_seq(T0.data(), E.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, rp,
+    rcalib_seq(T0.data(), E.data(), cams.data(), fb.data(), N, C, W, H, X.data(), n, 0, cand.data(), nc, p, rp,
                    T_out.data(), res, nullptr);
-    CHECK(res.status == rc::kStarved && res.n_obs_cam[0][C - 1] == 0 && res.n_obs[0] > 12 * N);
+    CHECK(res.status == lc::kStarved && res.n_obs_cam[0][C - 1] == 0 && res.n_obs[0] > 12 * N);
     CHECK(res.K[C - 1][0] == nominal.fx);
     // no candidates at all
-    rc::rcalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), 0, p, rp,
+    rcalib_seq(T0.data(), E.data(), cams.data(), frames.data(), N, C, W, H, X.data(), n, 0, cand.data(), 0, p, rp,
                    T_out.data(), res, nullptr);
-    CHECK(res.status == rc::kStarved && res.rms[0] == 0.0);
+    CHECK(res.status == lc::kStarved && res.rms[0] == 0.0);
   }
 }
 
