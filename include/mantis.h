@@ -976,8 +976,10 @@ mantis_status mantis_mcl_refine_modes(void* ctx, const mantis_image* cams, int32
  * stays 5 (find the entries by name, check the sizes with mantis_calib_sizes).
  * The caller's mantis_images are never written; the context's prior, cv::RNG
  * state and robust setting (mantis_refine_set_robust) are neither read nor
- * changed. Robust rows do not apply here: a drifted camera is modelled, not
- * down-weighted.
+ * changed. The refinement's robust rows do not apply here: a drifted camera
+ * is modelled, not down-weighted. The calibrations have a switch of their own
+ * (mantis_calib_set_robust, below) against a bad minority of rows -- one view
+ * with a knocked camera, a foreign line, an occluder.
  *
  * Unknowns and the gauge. T_r = T_w_b of view r < N, and E_c = T_base_cam of
  * camera c for every bit c set in free_cams. At least one camera must be held
@@ -1319,6 +1321,82 @@ mantis_status mantis_calibrate_rig(void* ctx, const mantis_image* cams, int32_t 
 mantis_status mantis_get_rcalib_record(void* ctx, int32_t rig, int32_t pass, double* T_w_b, double* T_base_cam,
                                        double* KD, int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows,
                                        double* acc231);
+
+/* ---- Calibration, robust rows: Huber / Tukey weights from a call-wide median ----
+ * The three calibrations above give every code-0 row the same weight, and what
+ * they return is taken as exact by every later call: a camera knocked in one of
+ * the N views, a foreign line or an occluder in one frame ends up in
+ * T_base_cam, K and D. With this switch on, every pass reweights its rows as
+ * the line refinement's robust rows do, but from one scale over the whole call
+ * (all views and cameras): one joint solve has one noise scale, and a median
+ * per view would be blind to a view that is wrong as a whole. Off by default
+ * and switched per context; all addition: no struct above changes its size,
+ * MANTIS_ABI_VERSION stays 5 (find the entries by name, check the sizes with
+ * mantis_calib_robust_sizes), and with the switch off the three calibrations
+ * return the bytes they returned before and launch the kernels they launched
+ * before. The switch is independent of mantis_refine_set_robust in both
+ * directions.
+ *
+ * At every pass k = 0 .. I, after the observations and before the accumulation:
+ *  1. key of a code-0 slot = floor(|Skw| 2^20 / Sw), the refinement's key.
+ *     Rejected slots have key 0 and weight 0 in the record.
+ *  2. n = the code-0 count over all N C n_cand slots of the call, m = the key
+ *     of rank floor((n - 1) / 2) among them in ascending order; n = 0: m = 0.
+ *  3. sigma = max(1.4826 ((double)m / 2^20), scale_floor).
+ *  4. w = the refinement's weight of (key, loss, tuning, sigma).
+ *  5. the accumulated row is sqrt(w) [J ... | r], all 13, 15 or 21 columns.
+ *  6. n_obs, n_obs_cam and the record's rows stay the unweighted code-0
+ *     figures; rms, rms_cam, the covariances and every solve take the weighted
+ *     accumulators (rms = sqrt(r^T W r / n_obs)).
+ *  7. STARVED also when a view has fewer than min_obs rows with w > 0,
+ *  8. and when a camera free in either mask has fewer than min_obs_cam rows
+ *     with w > 0. Both also clear `calibrated` on the final pass.
+ *  9. the end of the pass, dof, the gate and the covariances are otherwise
+ *     those of the calibration, on the weighted accumulators.
+ * 10. I = 0 returns every input bit for bit; the stats of pass 0 are filled.
+ * Device work with the switch on: 5 (I + 1) launches (k_*_obs, k_*_hist twice,
+ * k_*_rig, k_*_solve per pass; the selection of m spans the views' blocks and
+ * every hand-off is a kernel boundary), one memset of the selection tables
+ * before the first pass and one more copy back (the stats). */
+typedef struct mantis_calib_robust_stats {
+  int32_t loss, kind;          /* kind: 0 extrinsic, 1 intrinsic, 2 rig */
+  int32_t n_rigs, n_cams;
+  uint32_t median_key[11];     /* per pass; entries past iterations_run are 0 */
+  int32_t n_down[11];          /* rows with w < 1, over the call */
+  int32_t n_zero[11];          /* rows with w == 0 */
+  int32_t pad;
+  double scale[11];            /* sigma */
+  double sum_w[11];            /* sum of w over the code-0 rows, in (view, camera) order */
+  /* of the last pass run (iterations_run); zeros past n_rigs / n_cams */
+  int32_t n_obs_view[256];     /* code-0 rows of the view over its cameras */
+  int32_t n_zero_view[256];
+  double sum_w_view[256];      /* a wrong view has a low sum_w_view / n_obs_view */
+  int32_t n_zero_cam[8];
+  double sum_w_cam[8];         /* against n_obs_cam[iterations_run][c] of the result */
+} mantis_calib_robust_stats;
+/* sizeof(mantis_refine_robust_params) (the parameters are the refinement's
+ * struct), sizeof(mantis_calib_robust_stats) (host only) */
+void mantis_calib_robust_sizes(int32_t* params_bytes, int32_t* stats_bytes);
+
+/* The context's setting for all three calibrations: NULL or loss = 0 switches
+ * the robust rows off. Defaults: mantis_default_refine_robust_params. Kept
+ * across calls, applies from the next calibration. Host only. MANTIS_ERR_ARG
+ * (the setting stays; mantis_last_error names the field): struct_size, loss
+ * outside 0..2, tuning or scale_floor not finite and > 0. */
+mantis_status mantis_calib_set_robust(void* ctx, const mantis_refine_robust_params* p);
+/* The stats of the last calibration of `kind` (0 extrinsic, 1 intrinsic, 2
+ * rig; each kind keeps its own). MANTIS_ERR_STATE: no call of that kind yet,
+ * or its last call ran with the switch off. MANTIS_ERR_ARG: null, kind outside
+ * 0..2. */
+mantis_status mantis_get_calib_robust(void* ctx, int32_t kind, mantis_calib_robust_stats* stats);
+/* Keys and weights (each nullable) of view `rig`, pass 0 .. iterations_run, of
+ * the last calibration of `kind`, which must have run with the switch on and
+ * record = 1 (else MANTIS_ERR_STATE): one entry per slot (C x n_cand), 0 in
+ * rejected slots. mantis_get_calib_record and its two siblings keep returning
+ * the unweighted rows; their accumulators are the weighted ones the pass
+ * solved. MANTIS_ERR_ARG: kind, rig or pass out of range. */
+mantis_status mantis_get_calib_robust_record(void* ctx, int32_t kind, int32_t rig, int32_t pass, uint32_t* keys,
+                                             double* weights);
 
 #ifdef __cplusplus
 }

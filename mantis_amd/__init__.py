@@ -124,6 +124,14 @@ class MantisRefineRobustStats(C.Structure):
                 ("n_zero", C.c_int32 * 11), ("scale", C.c_double * 11), ("sum_w", C.c_double * 11)]
 
 
+class MantisCalibRobustStats(C.Structure):
+    _fields_ = [("loss", C.c_int32), ("kind", C.c_int32), ("n_rigs", C.c_int32), ("n_cams", C.c_int32),
+                ("median_key", C.c_uint32 * 11), ("n_down", C.c_int32 * 11), ("n_zero", C.c_int32 * 11),
+                ("pad", C.c_int32), ("scale", C.c_double * 11), ("sum_w", C.c_double * 11),
+                ("n_obs_view", C.c_int32 * 256), ("n_zero_view", C.c_int32 * 256), ("sum_w_view", C.c_double * 256),
+                ("n_zero_cam", C.c_int32 * 8), ("sum_w_cam", C.c_double * 8)]
+
+
 class MantisMclModeRefined(C.Structure):
     _fields_ = [("applied", C.c_int32), ("key_kept", C.c_int32), ("n_moved", C.c_int32), ("pad", C.c_int32),
                 ("refine", MantisRefineResult)]
@@ -329,6 +337,11 @@ _SIGS = {
                                        C.POINTER(MantisRefineParams), C.POINTER(MantisRcalibParams), C.c_void_p,
                                        C.POINTER(MantisRcalibResult)]),
     "mantis_get_rcalib_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "mantis_calib_robust_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_calib_set_robust": (C.c_int, [C.c_void_p, C.POINTER(MantisRefineRobustParams)]),
+    "mantis_get_calib_robust": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MantisCalibRobustStats)]),
+    "mantis_get_calib_robust_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                 C.c_void_p]),
     "mantis_mcl_refine_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mantis_mcl_refine_modes": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32,
                                           C.POINTER(MantisRefineParams), C.c_int32, C.POINTER(MantisMclRefined)]),
@@ -904,6 +917,50 @@ class Mantis:
                                                  acc.ctypes.data),
                   "get_rcalib_record")
         return T, E, KD, codes, Sw, Skw, rows, acc
+
+    # the calibrations' robust rows (mantis_calib_set_robust, include/mantis.h) ----
+    CALIB_KINDS = {"ext": 0, "int": 1, "rig": 2}
+
+    def set_calib_robust(self, loss=None, **params):
+        """mantis_calib_set_robust: the robust rows of every later calibration
+        on this context (all three kinds). loss: None (NULL: off), 0 / "none",
+        1 / "huber", 2 / "tukey"; `tuning` and `scale_floor` override
+        mantis_default_refine_robust_params."""
+        if loss is None and not params:
+            self._chk(lib().mantis_calib_set_robust(self.h, None), "calib_set_robust")
+            return
+        p = MantisRefineRobustParams()
+        lib().mantis_default_refine_robust_params(self.REFINE_LOSSES.get(loss, loss), C.byref(p))
+        for k, v in params.items():
+            if k not in ("tuning", "scale_floor"):
+                raise TypeError(f"calib robust: unknown parameter {k!r}")
+            setattr(p, k, v)
+        self._chk(lib().mantis_calib_set_robust(self.h, C.byref(p)), "calib_set_robust")
+
+    def calib_robust_stats(self, kind):
+        """mantis_get_calib_robust: the MantisCalibRobustStats of the last
+        calibration of `kind` (0 / "ext", 1 / "int", 2 / "rig"), made with the
+        robust rows on."""
+        st = MantisCalibRobustStats()
+        self._chk(lib().mantis_get_calib_robust(self.h, self.CALIB_KINDS.get(kind, kind), C.byref(st)),
+                  "get_calib_robust")
+        return st
+
+    def calib_robust_record(self, kind, rig, pass_):
+        """mantis_get_calib_robust_record: (keys uint32 [slots], weights
+        [slots]) of pass `pass_` of view `rig` of the last calibration of
+        `kind`, made with the robust rows on and record=1; 0 in rejected slots."""
+        kind = self.CALIB_KINDS.get(kind, kind)
+        names = ("_calib_shape", "_icalib_shape", "_rcalib_shape")
+        shape = getattr(self, names[kind], None) if kind in (0, 1, 2) else (0, 0)  # a wrong kind: the library's error
+        if shape is None:
+            raise MantisError("calib_robust_record: no calibration of that kind on this context")
+        ns = shape[0] * shape[1]
+        keys = np.zeros(ns, np.uint32)
+        w = np.zeros(ns)
+        self._chk(lib().mantis_get_calib_robust_record(self.h, kind, rig, pass_, keys.ctypes.data, w.ctypes.data),
+                  "get_calib_robust_record")
+        return keys, w
 
     # Monte Carlo localization (mantis_mcl_*, include/mantis.h) ---------------
     def mcl_params(self, **params):

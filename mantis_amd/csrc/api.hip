@@ -373,9 +373,20 @@ struct Ctx {
     void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
     int view_cap = 0;
     size_t slot_cap = 0, racc_cap = 0;
-    bool lds_asked = false, lds_ok = false;
+    bool lds_asked[2] = {false, false}, lds_ok[2] = {false, false};  // [robust rows off, on]: two instantiations
     int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
+    // the robust rows (mantis_calib_set_robust): every slot's key, laid out as d_slots; the
+    // weights, only as a record; the selection tables of every pass; the (view, camera) cells of
+    // a pass; the stats (d: of the call, h: pinned, of the last call) and the last call's loss
+    uint32_t *d_rkeys = nullptr, *d_rtab = nullptr;
+    double* d_rweights = nullptr;
+    void* d_rcells = nullptr;
+    mantis_calib_robust_stats *d_rstats = nullptr, *h_rstats = nullptr;
+    size_t rkey_cap = 0, rweight_cap = 0;
+    int rcell_cap = 0, rec_loss = 0;
   } cb, ib, rb;  // extrinsic, intrinsic, rig
+  // what mantis_calib_set_robust left for the three of them (loss 0 until then)
+  mantis_refine_robust_params calib_robust{};
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1440,10 +1451,12 @@ mantis_status mantis_destroy(void* ctx) {
   if (c->rf.h_rstats) (void)hipHostFree(c->rf.h_rstats);
   for (Ctx::Linecal* k : {&c->cb, &c->ib, &c->rb}) {
     void* kptrs[] = {k->d_state, k->d_T, k->d_acc, k->d_Y, k->d_Wt, k->d_cnt, k->d_pd,
-                     k->d_recT, k->d_recE, k->d_recKD, k->d_recAcc, k->d_slots};
+                     k->d_recT, k->d_recE, k->d_recKD, k->d_recAcc, k->d_slots,
+                     k->d_rkeys, k->d_rtab, k->d_rweights, k->d_rcells, k->d_rstats};
     for (void* p : kptrs)
       if (p) (void)hipFree(p);
     if (k->h_state) (void)hipHostFree(k->h_state);
+    if (k->h_rstats) (void)hipHostFree(k->h_rstats);
   }
   for (void* p : c->user_allocs) (void)hipFree(p);
   void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,

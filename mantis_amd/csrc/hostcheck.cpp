@@ -707,7 +707,8 @@ void lc_accumulate(const double* rows, int n, double* acc) {
 template <class P>
 void lc_seq(const double* T_in, const double* Tbc, const double* K, const double* D, const uint8_t* const* frames, int N,
             int C, int W, int H, const double* X, int nw, int nr, int ng, const mantis_refine_params* p, uint32_t fe,
-            uint32_t fi, uint32_t pm, int32_t min_obs_cam, double* T_out, mantis_rcalib_result* out) {
+            uint32_t fi, uint32_t pm, int32_t min_obs_cam, double* T_out, mantis_rcalib_result* out,
+            const mantis_refine_robust_params* rb = nullptr, mantis_calib_robust_stats* stats = nullptr) {
   namespace rf = mk::refine;
   const int n = nw + nr + ng;
   std::vector<uint8_t> flags(n > 0 ? n : 1);
@@ -716,8 +717,9 @@ void lc_seq(const double* T_in, const double* Tbc, const double* K, const double
   const int nc = rf::candidates(flags.data(), n, cand.data());
   std::vector<mk::Cam> cm(C);
   for (int c = 0; c < C; c++) cm[c] = hc_cam(K + 9 * c, D + 4 * c);
+  const rf::Robust r = rb ? rf::Robust{rb->loss, 0, rb->tuning, rb->scale_floor} : rf::Robust{0, 0, 1.0, 1.0};
   P::seq(T_in, Tbc, cm.data(), frames, N, C, W, H, X, nw, nr, cand.data(), nc, *p, fe, fi, pm, min_obs_cam, T_out, *out,
-         nullptr);
+         nullptr, &r, stats);
 }
 }  // namespace
 }  // extern "C++"
@@ -820,6 +822,94 @@ void hc_rcalib_conclude(const double* acc231, const int32_t* cnt, int N, int C, 
 }
 int hc_sizeof_rcalib_params(void) { return (int)sizeof(mantis_rcalib_params); }
 int hc_sizeof_rcalib_result(void) { return (int)sizeof(mantis_rcalib_result); }
+
+// The calibrations' robust rows (mk_linecal.h robust_*): the rules k_linecal_hist and the robust
+// instantiations of k_linecal_rig / k_linecal_solve run. One pass over all N x C x n_cand slots
+// (view-major): keys and weights (0 in rejected slots), the call-wide lower median and scale,
+// counts (4: n_obs, n_down, n_zero, n with w > 0), sum_w in slot order, and per (view, camera)
+// cell_counts (N x C x 2: n_down, n_zero) and cell_sum_w (N x C)
+void hc_linecal_robust_weights(const int32_t* codes, const int32_t* Sw, const int32_t* Skw, int N, int C, int n_cand,
+                               int loss, double tuning, double scale_floor, uint32_t* keys, double* weights,
+                               uint32_t* median_key, double* scale, int32_t* counts, double* sum_w,
+                               int32_t* cell_counts, double* cell_sum_w) {
+  mk::refine::RobustPass P;
+  std::vector<lc::RobustCell> cells((size_t)N * C);
+  lc::robust_pass(codes, Sw, Skw, N, C, n_cand, mk::refine::Robust{loss, 0, tuning, scale_floor}, keys, weights,
+                  cells.data(), P);
+  *median_key = P.median_key;
+  *scale = P.scale;
+  counts[0] = P.n_obs;
+  counts[1] = P.n_down;
+  counts[2] = P.n_zero;
+  counts[3] = P.n_obs - P.n_zero;
+  *sum_w = P.sum_w;
+  for (int f = 0; f < N * C; f++) {
+    cell_counts[2 * f] = cells[f].n_down;
+    cell_counts[2 * f + 1] = cells[f].n_zero;
+    cell_sum_w[f] = cells[f].sum_w;
+  }
+}
+// the stats of a pass from its cells (as hc_linecal_robust_weights lays them out) and counts
+void hc_linecal_robust_tally(const int32_t* cell_counts, const double* cell_sum_w, const int32_t* cnt, int N, int C,
+                             int pass, uint32_t median_key, double sigma, mantis_calib_robust_stats* stats) {
+  std::vector<lc::RobustCell> cells((size_t)N * C);
+  for (int f = 0; f < N * C; f++) cells[f] = lc::RobustCell{cell_counts[2 * f], cell_counts[2 * f + 1], cell_sum_w[f]};
+  lc::robust_tally(cells.data(), cnt, N, C, pass, median_key, sigma, *stats);
+}
+// hc_*_seq with the robust rows of rb (null or loss 0: hc_*_seq's bytes); stats nullable
+void hc_calib_seq_robust(const double* T_in, const double* Tbc, const double* K, const double* D,
+                         const uint8_t* const* frames, int N, int C, int W, int H, const double* X, int nw, int nr,
+                         int ng, const mantis_refine_params* p, const mantis_calib_params* cp,
+                         const mantis_refine_robust_params* rb, double* T_out, mantis_calib_result* out,
+                         mantis_calib_robust_stats* stats) {
+  mantis_rcalib_result w;
+  lc_seq<lc::Ext>(T_in, Tbc, K, D, frames, N, C, W, H, X, nw, nr, ng, p, (uint32_t)cp->free_cams, 0u, 0u,
+                  cp->min_obs_cam, T_out, &w, rb, stats);
+  lc::narrow(w, *out);
+}
+void hc_icalib_seq_robust(const double* T_in, const double* Tbc, const double* K, const double* D,
+                          const uint8_t* const* frames, int N, int C, int W, int H, const double* X, int nw, int nr,
+                          int ng, const mantis_refine_params* p, const mantis_icalib_params* ip,
+                          const mantis_refine_robust_params* rb, double* T_out, mantis_icalib_result* out,
+                          mantis_calib_robust_stats* stats) {
+  mantis_rcalib_result w;
+  lc_seq<lc::Int>(T_in, Tbc, K, D, frames, N, C, W, H, X, nw, nr, ng, p, 0u, (uint32_t)ip->free_cams,
+                  (uint32_t)ip->param_mask, ip->min_obs_cam, T_out, &w, rb, stats);
+  lc::narrow(w, *out);
+}
+void hc_rcalib_seq_robust(const double* T_in, const double* Tbc, const double* K, const double* D,
+                          const uint8_t* const* frames, int N, int C, int W, int H, const double* X, int nw, int nr,
+                          int ng, const mantis_refine_params* p, const mantis_rcalib_params* rp,
+                          const mantis_refine_robust_params* rb, double* T_out, mantis_rcalib_result* out,
+                          mantis_calib_robust_stats* stats) {
+  lc_seq<lc::Rig>(T_in, Tbc, K, D, frames, N, C, W, H, X, nw, nr, ng, p, (uint32_t)rp->free_ext, (uint32_t)rp->free_int,
+                  (uint32_t)rp->param_mask, rp->min_obs_cam, T_out, out, rb, stats);
+}
+// hc_*_end_pass with the robust rows' two starved gates: pos (N x C) = the rows with w > 0
+int hc_calib_end_pass_robust(const double* acc91, const int32_t* cnt, const int32_t* pos, int N, int C, int free_cams,
+                             int pass, int I, int min_obs, int min_obs_cam, double lambda, double* T,
+                             mantis_calib_result* R, double* delta) {
+  return lc::with_state(*R, [&](mantis_rcalib_result& w) {
+    return lc::Ext::end_pass(acc91, cnt, N, C, (uint32_t)free_cams, 0u, 0u, pass, I, min_obs, min_obs_cam, lambda, T, w,
+                             delta, pos) ? 1 : 0;
+  });
+}
+int hc_icalib_end_pass_robust(const double* acc120, const int32_t* cnt, const int32_t* pos, int N, int C, int free_cams,
+                              int param_mask, int pass, int I, int min_obs, int min_obs_cam, double lambda, double* T,
+                              mantis_icalib_result* R, double* delta) {
+  return lc::with_state(*R, [&](mantis_rcalib_result& w) {
+    return lc::Int::end_pass(acc120, cnt, N, C, 0u, (uint32_t)free_cams, (uint32_t)param_mask, pass, I, min_obs,
+                             min_obs_cam, lambda, T, w, delta, pos) ? 1 : 0;
+  });
+}
+int hc_rcalib_end_pass_robust(const double* acc231, const int32_t* cnt, const int32_t* pos, int N, int C, int free_ext,
+                              int free_int, int param_mask, int pass, int I, int min_obs, int min_obs_cam,
+                              double lambda, double* T, mantis_rcalib_result* R, double* delta) {
+  return lc::Rig::end_pass(acc231, cnt, N, C, (uint32_t)free_ext, (uint32_t)free_int, (uint32_t)param_mask, pass, I,
+                           min_obs, min_obs_cam, lambda, T, *R, delta, pos)
+             ? 1 : 0;
+}
+int hc_sizeof_calib_robust_stats(void) { return (int)sizeof(mantis_calib_robust_stats); }
 
 // The modes refined (mk_mcl_refine.h): the rules mantis_mcl_refine_modes and k_mcl_recentre run.
 // modes: a struct mantis_mcl_modes; T_ref 8 x 16 (row-major), refined 8; out: key_kept / applied (8

@@ -49,6 +49,77 @@ struct Layout {
   int32_t fe[kMaxCams], fi[kMaxCams];
 };
 
+// ---- robust rows (mantis_calib_set_robust, include/mantis.h): the refinement's
+// key, scale and weight (refine::robust_key / _scale / _weight, not restated)
+// with the median taken over every slot of the call, so one sigma per pass.
+// Per (view, camera) the device's k_linecal_rig and the host keep a cell; the
+// gates and the stats are formed from the cells in (view, camera) order.
+struct RobustCell {
+  int32_t n_down, n_zero;  // rows with w < 1, with w == 0
+  double sum_w;
+};
+constexpr int kKindExt = 0, kKindInt = 1, kKindRig = 2;  // mantis_get_calib_robust's `kind`
+
+// the rows with w > 0 per (view, camera): what the two extra starved gates count
+MK_HD void robust_pos(const RobustCell* cells, const int32_t* cnt, int n, int32_t* pos) {
+  for (int k = 0; k < n; k++) pos[k] = cnt[k] - cells[k].n_zero;
+}
+// The stats of pass `pass` from its cells (N x C) and counts: the pass's
+// figures, and the per-view and per-camera figures of this pass (the last pass
+// run leaves them). sum_w_view in camera order, sum_w_cam in view order, the
+// pass's sum_w = the views' sums in view order.
+MK_HD void robust_tally(const RobustCell* cells, const int32_t* cnt, int N, int C, int pass, uint32_t median_key,
+                        double sigma, mantis_calib_robust_stats& st) {
+  int32_t down = 0, zero = 0;
+  double sw = 0.0;
+  for (int c = 0; c < kMaxCams; c++) {
+    st.n_zero_cam[c] = 0;
+    st.sum_w_cam[c] = 0.0;
+  }
+  for (int r = 0; r < kMaxViews; r++) {
+    st.n_obs_view[r] = st.n_zero_view[r] = 0;
+    st.sum_w_view[r] = 0.0;
+  }
+  for (int r = 0; r < N; r++) {
+    for (int c = 0; c < C; c++) {
+      const RobustCell& q = cells[r * C + c];
+      down += q.n_down;
+      zero += q.n_zero;
+      st.n_obs_view[r] += cnt[r * C + c];
+      st.n_zero_view[r] += q.n_zero;
+      st.sum_w_view[r] += q.sum_w;
+      st.n_zero_cam[c] += q.n_zero;
+      st.sum_w_cam[c] += q.sum_w;
+    }
+    sw += st.sum_w_view[r];
+  }
+  st.median_key[pass] = median_key;
+  st.scale[pass] = sigma;
+  st.n_down[pass] = down;
+  st.n_zero[pass] = zero;
+  st.sum_w[pass] = sw;
+}
+// Host: the rule over one pass's slots (view-major, then camera, then
+// candidate). keys / weights (N C n_cand each): 0 in rejected slots; cells: N x
+// C, sum_w in slot order; P: the call-wide median, sigma and counts.
+inline void robust_pass(const int32_t* codes, const int32_t* Sw, const int32_t* Skw, int N, int C, int n_cand,
+                        const refine::Robust& rb, uint32_t* keys, double* weights, RobustCell* cells,
+                        refine::RobustPass& P) {
+  const int n = N * C * n_cand;
+  for (int k = 0; k < n; k++) keys[k] = codes[k] == 0 ? refine::robust_key(Sw[k], Skw[k]) : 0u;
+  refine::robust_weights(keys, codes, n, rb, weights, P);
+  for (int f = 0; f < N * C; f++) {
+    RobustCell q{0, 0, 0.0};
+    for (int k = f * n_cand; k < (f + 1) * n_cand; k++) {
+      if (codes[k] != 0) continue;
+      q.n_down += weights[k] < 1.0;
+      q.n_zero += weights[k] == 0.0;
+      q.sum_w += weights[k];
+    }
+    cells[f] = q;
+  }
+}
+
 // ---- host: the views' elimination and the reduced system as plain loops ----
 struct Reduced {
   std::vector<double> Y, Wt, S, L, Ld;  // N x 6 x kLd, N x kMaxS x kLd, kMaxS x kLd twice, kMaxS
@@ -321,13 +392,16 @@ struct Problem {
   // when the call is finished (the final pass, STARVED, SINGULAR or DIVERGED);
   // otherwise T (N x 16), R.T_base_cam and R.K / R.D are the next estimates,
   // delta (N x 6, nullable) the poses' steps and R.delta_ext[pass] /
-  // R.delta_int[pass] the cameras'.
+  // R.delta_int[pass] the cameras'. With the robust rows acc is the weighted
+  // one and pos (N x C, else null) the rows with w > 0: too few of them in a
+  // view or a free camera starve the pass too.
   static bool end_pass(const double* acc, const int32_t* cnt, int N, int C, uint32_t free_ext, uint32_t free_int,
                        uint32_t param_mask, int pass, int I, int32_t min_obs, int32_t min_obs_cam, double lambda,
-                       double* T, mantis_rcalib_result& R, double* delta) {
+                       double* T, mantis_rcalib_result& R, double* delta, const int32_t* pos = nullptr) {
     tally(acc, cnt, N, C, pass, R);
     if (pass >= I) return true;
-    if (starved(cnt, N, C, free_ext, free_int, min_obs, min_obs_cam)) {
+    if (starved(cnt, N, C, free_ext, free_int, min_obs, min_obs_cam) ||
+        (pos && starved(pos, N, C, free_ext, free_int, min_obs, min_obs_cam))) {
       R.status = kStarved;
       return true;
     }
@@ -380,10 +454,11 @@ struct Problem {
   // positive definite. cov_ext[c] / cov_int[c] = (r^T r / dof) (S^-1)_cc, the
   // marginal over the poses; cov_ext in the order x, y, z, rot-x, rot-y, rot-z
   // of the right perturbation; R.K holds the final intrinsics: they scale
-  // cov_int to natural units. Otherwise zeros.
+  // cov_int to natural units. Otherwise zeros. pos (nullable): end_pass's, of
+  // the last pass; its two gates count as starved gates here too.
   static void conclude(const double* acc, const int32_t* cnt, int N, int C, uint32_t free_ext, uint32_t free_int,
                        uint32_t param_mask, int32_t min_obs, int32_t min_obs_cam, double max_rms,
-                       mantis_rcalib_result& R) {
+                       mantis_rcalib_result& R, const int32_t* pos = nullptr) {
     const int fp = R.iterations_run;
     for (int c = 0; c < kMaxCams; c++) {
       R.rms_cam[c] = 0.0;
@@ -401,6 +476,7 @@ struct Problem {
     for (int e = 0; e < kPi; e++) np += (int)(param_mask >> e & 1u);
     const int64_t dof = (int64_t)R.n_obs[fp] - 6 * (int64_t)N - 6 * (int64_t)l.Fe - (int64_t)np * l.Fi;
     R.calibrated = R.status == kOk && !starved(cnt, N, C, free_ext, free_int, min_obs, min_obs_cam) &&
+                   !(pos && starved(pos, N, C, free_ext, free_int, min_obs, min_obs_cam)) &&
                    (max_rms <= 0 || R.rms[fp] <= max_rms) && dof > 0;
     if (!R.calibrated) return;
     Reduced w;
@@ -443,11 +519,23 @@ struct Problem {
   // Tbc: the starting extrinsics, C x 16; cams: the starting intrinsics (K
   // already rounded to float); T_in / T_out: N x 16. slots (nullable): N x C x
   // n_cand of the last pass taken. A problem without a block takes 0 for its
-  // mask (and for param_mask without J_int).
+  // mask (and for param_mask without J_int). rb (nullable; loss 0 is null): the
+  // robust rows -- every pass first takes all its slots, then weighs them from
+  // the call-wide median and sums sqrt(w) row in slot order; stats (nullable)
+  // are filled only then.
   static void seq(const double* T_in, const double* Tbc, const Cam* cams, const uint8_t* const* frames, int N, int C,
                   int W, int H, const double* X, int nw, int nr, const int32_t* cand, int n_cand,
                   const mantis_refine_params& p, uint32_t fe, uint32_t fi, uint32_t pm, int32_t min_obs_cam,
-                  double* T_out, mantis_rcalib_result& R, Slot* slots) {
+                  double* T_out, mantis_rcalib_result& R, Slot* slots, const refine::Robust* rb = nullptr,
+                  mantis_calib_robust_stats* stats = nullptr) {
+    if (rb && rb->loss == refine::kLossNone) rb = nullptr;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (rb && stats) {
+      stats->loss = rb->loss;
+      stats->kind = kE && kI ? kKindRig : kI ? kKindInt : kKindExt;
+      stats->n_rigs = N;
+      stats->n_cams = C;
+    }
     std::memset(&R, 0, sizeof(R));
     R.n_cand = n_cand;
     R.n_rigs = N;
@@ -468,7 +556,59 @@ struct Problem {
     const refine::Window win{p.half_window, p.white_thresh, p.min_weight, 0};
     std::vector<double> acc((size_t)N * C * kAcc);
     std::vector<int32_t> cnt((size_t)N * C);
+    // the robust rows' pass: its slots, codes and sums, keys, weights, cells and rows with w > 0
+    const size_t ns = rb ? (size_t)N * C * n_cand : 0;
+    std::vector<Slot> all(ns);
+    std::vector<int32_t> codes(ns), Sw(ns), Skw(ns), pos(rb ? (size_t)N * C : 0);
+    std::vector<uint32_t> keys(ns);
+    std::vector<double> wts(ns);
+    std::vector<RobustCell> cells(rb ? (size_t)N * C : 0);
     for (int pass = 0; pass <= p.iterations; pass++) {
+      for (int r = 0; r < N && rb; r++) {
+        double Rt[9], t[3];
+        refine::pose_parts(T_out + 16 * (size_t)r, Rt, t);
+        for (int c = 0; c < C; c++) {
+          GnCam gc;
+          refine::gncam_from(R.T_base_cam[c], gc);
+          const Cam cm = icalib::cam_of(R.K[c], R.D[c]);
+          for (int k = 0; k < n_cand; k++) {
+            const int i = cand[k] & 0xffff, axis = cand[k] >> 16;
+            int tg[3];
+            refine::target_bgr(i, nw, nr, tg);
+            const size_t q = ((size_t)r * C + c) * n_cand + k;
+            observe(Rt, t, gc, cm, frames[r * C + c], W, H, X + 3 * i, axis, tg, win, (fe >> c & 1) != 0,
+                    (fi >> c & 1) != 0, pm, all[q], nullptr);
+            codes[q] = all[q].code;
+            Sw[q] = all[q].Sw;
+            Skw[q] = all[q].Skw;
+          }
+        }
+      }
+      if (rb) {
+        refine::RobustPass P;
+        robust_pass(codes.data(), Sw.data(), Skw.data(), N, C, n_cand, *rb, keys.data(), wts.data(), cells.data(), P);
+        for (int f = 0; f < N * C; f++) {
+          double* a = acc.data() + (size_t)kAcc * f;
+          for (int e = 0; e < kAcc; e++) a[e] = 0.0;
+          int32_t n = 0;
+          for (int k = 0; k < n_cand; k++) {
+            const size_t q = (size_t)f * n_cand + k;
+            const double sq = sqrt(wts[q]);
+            double v[kRow];
+            for (int e = 0; e < kRow; e++) v[e] = all[q].row[e] * sq;
+            accumulate_row(v, a);
+            n += codes[q] == 0;
+          }
+          cnt[f] = n;
+        }
+        if (slots) std::memcpy(slots, all.data(), sizeof(Slot) * ns);
+        robust_pos(cells.data(), cnt.data(), N * C, pos.data());
+        if (stats) robust_tally(cells.data(), cnt.data(), N, C, pass, P.median_key, P.scale, *stats);
+        if (end_pass(acc.data(), cnt.data(), N, C, fe, fi, pm, pass, p.iterations, p.min_obs, min_obs_cam, p.lambda,
+                     T_out, R, nullptr, pos.data()))
+          break;
+        continue;
+      }
       for (int r = 0; r < N; r++) {
         double Rt[9], t[3];
         refine::pose_parts(T_out + 16 * (size_t)r, Rt, t);
@@ -497,7 +637,7 @@ struct Problem {
                    R, nullptr))
         break;
     }
-    conclude(acc.data(), cnt.data(), N, C, fe, fi, pm, p.min_obs, min_obs_cam, p.max_rms, R);
+    conclude(acc.data(), cnt.data(), N, C, fe, fi, pm, p.min_obs, min_obs_cam, p.max_rms, R, rb ? pos.data() : nullptr);
   }
 };
 
