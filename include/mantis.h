@@ -1398,6 +1398,137 @@ mantis_status mantis_get_calib_robust(void* ctx, int32_t kind, mantis_calib_robu
 mantis_status mantis_get_calib_robust_record(void* ctx, int32_t kind, int32_t rig, int32_t pass, uint32_t* keys,
                                              double* weights);
 
+/* ---- Window smoothing: line rows plus odometry factors over N views ----
+ * Every refine and calibration entry above treats the views of a call as
+ * independent rig poses. This call ties N consecutive views of one rig
+ * together with the service's motions (mantis_motion) and solves the short
+ * trajectory jointly: a view that sees too few lines (STARVED on its own) is
+ * held by its factors, and every view gets a marginal covariance that accounts
+ * for the odometry. All addition: no other entry point, struct, kernel result
+ * or draw changes, MANTIS_ABI_VERSION stays 5 (find the entries by name, check
+ * the sizes with mantis_smooth_sizes). Nothing is drawn from the cv::RNG, the
+ * context's prior pose is not touched, and the robust switches
+ * (mantis_refine_set_robust, mantis_calib_set_robust) are not read.
+ *
+ * A window: N views (1 <= N <= 256) of one rig of C cameras (1..8), frames
+ * cams[(w N + k) C + c], one size. View k starts at T_w_b_in[k]. Step k -> k+1
+ * (k = 0 .. N - 2) has motions[k]; Delta_k = Transform(delta_quat, delta_pos),
+ * formed as mantis_track / mantis_refine form their prediction, so T_k+1 ~
+ * T_k Delta_k. An unset motion (|q|^2 < 0.5) puts no factor on its step: the
+ * chain breaks there and the two sides are independent segments of one system.
+ *
+ * Rows: exactly the line refinement's (codes, Sw, Skw, the 7-column row, slot
+ * = c n_cand + candidate). Per view A_k = J^T J, b_k = J^T r, r^T r (acc28)
+ * and n_obs_k. The line rows keep unit weight.
+ *
+ * Between factor of a set motion k, with the right perturbation T <- T D(x)
+ * of the refinement's step: M = T_k^-1 T_k+1 = [R_M | t_M], E = Delta_k^-1 M
+ * = [R_E | t_E], e = [t_E ; log R_E] (translation as is, rotation vector),
+ *   de/dx_k+1 = [[R_E, 0], [0, Jri]],
+ *   de/dx_k   = [[-R_D^T, R_D^T [t_M]x], [0, -Jri R_M^T]],
+ *   Jri = J_r^-1(e_r) = I + [phi]x / 2 + (1 / th^2 - (1 + cos th) / (2 th sin
+ *   th)) [phi]x^2, and I + [phi]x / 2 + [phi]x^2 / 12 for th < 1e-8.
+ * Whitening: rows 0..2 of e and of both Jacobians times sigma_row / sigma_t,
+ * rows 3..5 times sigma_row / sigma_rot.
+ * Prior factor (optional, view 0): e_p = [t_0 - t_p ; log(R_p^T R_0)],
+ * de_p/dx_0 = [[R_0, 0], [0, Jri]], whitened by sigma_row L_c^-1 with
+ * prior_cov = L_c L_c^T (Cholesky, host); prior_cov has the order and frames
+ * of mantis_refine_result.covariance (translation in the world frame, rotation
+ * a right perturbation).
+ *
+ * System of a pass, block tridiagonal in 6 x 6 blocks, every term added in
+ * this order: H_kk = A_k + Jb^T Jb (factor k - 1) + Ja^T Ja (factor k) + the
+ * prior's (k = 0) + lambda I; H_k+1,k = Jb^T Ja (factor k); g_k likewise from
+ * b_k and the J^T e terms (Ja = de/dx_k, Jb = de/dx_k+1, whitened). Solve by
+ * block Cholesky: L_kk = chol(H_kk - L_k,k-1 L_k,k-1^T), L_k+1,k = H_k+1,k
+ * L_kk^-T, forward and back substitution, every dot product in ascending index
+ * order; x = -H^-1 g, T_k <- T_k D(x_k).
+ *
+ * Pass p = 0 .. I: n_obs[p] = sum of the views' n_obs in view order, rms[p] =
+ * sqrt(r^T r / n_obs) over the rows only, motion_rms[p] = sqrt(sum e^T e / (6
+ * n_factors)) / sigma_row (about 1 when the odometry is as good as its sigmas
+ * say; 0 without factors), cost[p] = r^T r + sum e^T e (+ the prior's).
+ * STARVED when the window's n_obs < min_obs, SINGULAR when a diagonal block is
+ * not positive definite; either stops the whole window, which keeps the
+ * figures of the pass that stopped it at index iterations_run. A single blind
+ * view stops nothing. Pass I observes and solves nothing: I = 0 returns every
+ * input pose bit for bit.
+ *
+ * Gate and covariances (host, on the final pass's blocks at lambda = 0): dof =
+ * n_obs + 6 n_factors + 6 has_prior - 6 N, sigma2 = cost / dof; the marginals
+ * S_k are the diagonal blocks of H^-1 by the backward recursion S_N-1 = (L
+ * L^T)^-1, S_k = (L_kk L_kk^T)^-1 + G_k^T S_k+1 G_k, G_k = L_k+1,k L_kk^-1;
+ * covariance_k = sigma2 S_k with the translation block turned to the world
+ * frame by R_wb,k. smoothed = status OK && n_obs >= min_obs && (max_rms <= 0
+ * || rms <= max_rms) && dof > 0 && every block positive definite; otherwise
+ * the covariances are zeros. */
+typedef struct mantis_smooth_params {
+  int32_t struct_size;     /* sizeof(mantis_smooth_params) */
+  int32_t iterations;      /* I, 0..10 */
+  int32_t half_window;     /* R, 1..15 */
+  int32_t white_thresh;    /* 1..195075 */
+  int32_t min_weight;      /* >= 1 */
+  int32_t min_obs;         /* >= 6, of the window */
+  double lambda;           /* >= 0 */
+  double landmark_pitch;   /* > 0 */
+  double max_rms;          /* gate on the final rms; <= 0 means none */
+  double sigma_row;        /* finite and > 0: one line row, normalized image units */
+  double sigma_t;          /* finite and > 0: a step's translation, map units */
+  double sigma_rot;        /* finite and > 0: a step's rotation, rad */
+  int32_t record;          /* 1 = keep every pass (mantis_get_smooth_record / _pass) */
+  int32_t pad;
+} mantis_smooth_params;
+/* the refine defaults, then 0.00127 / 0.01 / 0.03 (0.41 px over fx = 323.15;
+ * mantis_mcl_params' per-step sigma_t / sigma_rot) */
+void mantis_default_smooth_params(mantis_smooth_params* p);
+
+typedef struct mantis_smooth_result { /* per window */
+  int32_t status, smoothed, iterations_run, n_cand; /* status: 0 OK, 1 STARVED, 2 SINGULAR */
+  int32_t n_views, n_factors, has_prior, dof;
+  int32_t n_obs[11];       /* per pass, of the window */
+  int32_t pad;
+  double rms[11];
+  double motion_rms[11];
+  double cost[11];
+  double sigma2;
+} mantis_smooth_result;
+typedef struct mantis_smooth_view { /* per window x view */
+  int32_t n_obs, pad;      /* of the last pass taken */
+  double rms;
+  double T_w_b[16];        /* smoothed base pose, row-major */
+  double covariance[36];   /* x, y, z, rot-x, rot-y, rot-z, row-major */
+} mantis_smooth_view;
+/* sizeof(mantis_smooth_params), sizeof(mantis_smooth_result), sizeof(mantis_smooth_view) (host only) */
+void mantis_smooth_sizes(int32_t* params_bytes, int32_t* result_bytes, int32_t* view_bytes);
+
+/* n_windows windows of n_views views by the rule above. T_w_b_in: n_windows x
+ * n_views x 16. motions: n_windows x (n_views - 1), NULL only when n_views ==
+ * 1. prior_T (n_windows x 16, nullable) with prior_cov (n_windows x 36, not
+ * null when prior_T is). out: per window; views: per window x view.
+ * MANTIS_ERR_ARG (nothing launched; mantis_last_error names the field): no
+ * map, n_windows x n_views x cams_per_rig > max_cams, n_views > 256,
+ * cams_per_rig > 8, frames of different sizes, a parameter outside its range,
+ * a pose or motion that is not finite, a prior covariance that is not finite
+ * or not positive definite, a null pointer. Device work: 3 (I + 1) launches on
+ * the context stream (k_refine_obs as it is with views as its rigs,
+ * k_smooth_acc, k_smooth_solve per pass), then one copy of the results. */
+mantis_status mantis_smooth_batch(void* ctx, const mantis_image* cams, int32_t n_windows, int32_t n_views,
+                                  int32_t cams_per_rig, const double* T_w_b_in, const mantis_motion* motions,
+                                  const double* prior_T, const double* prior_cov, const mantis_smooth_params* p,
+                                  mantis_smooth_result* out, mantis_smooth_view* views);
+/* Record of view `view` of window `window`, pass 0 .. iterations_run of that
+ * window, of the last smooth call made with record = 1: the shape of
+ * mantis_get_refine_record. MANTIS_ERR_STATE: no such record. MANTIS_ERR_ARG:
+ * an index out of range. */
+mantis_status mantis_get_smooth_record(void* ctx, int32_t window, int32_t view, int32_t pass, double* T_w_b,
+                                       int32_t* codes, int32_t* Sw, int32_t* Skw, double* rows, double* acc28);
+/* The pass-level record, each pointer nullable: e ((N - 1) x 6, whitened,
+ * zeros where no factor), J ((N - 1) x 72: Ja | Jb, whitened), prior_e (6),
+ * prior_J (36), delta (N x 6: the step the pass took; zeros on the pass that
+ * ended the window). Errors as mantis_get_smooth_record. */
+mantis_status mantis_get_smooth_pass(void* ctx, int32_t window, int32_t pass, double* e, double* J, double* prior_e,
+                                     double* prior_J, double* delta);
+
 #ifdef __cplusplus
 }
 #endif

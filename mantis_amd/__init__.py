@@ -115,6 +115,26 @@ class MantisRefineResult(C.Structure):
                 ("delta", (C.c_double * 6) * 10), ("covariance", C.c_double * 36)]
 
 
+class MantisSmoothParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("half_window", C.c_int32),
+                ("white_thresh", C.c_int32), ("min_weight", C.c_int32), ("min_obs", C.c_int32),
+                ("lambda_", C.c_double), ("landmark_pitch", C.c_double), ("max_rms", C.c_double),
+                ("sigma_row", C.c_double), ("sigma_t", C.c_double), ("sigma_rot", C.c_double),
+                ("record", C.c_int32), ("pad", C.c_int32)]
+
+
+class MantisSmoothResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("smoothed", C.c_int32), ("iterations_run", C.c_int32), ("n_cand", C.c_int32),
+                ("n_views", C.c_int32), ("n_factors", C.c_int32), ("has_prior", C.c_int32), ("dof", C.c_int32),
+                ("n_obs", C.c_int32 * 11), ("pad", C.c_int32), ("rms", C.c_double * 11),
+                ("motion_rms", C.c_double * 11), ("cost", C.c_double * 11), ("sigma2", C.c_double)]
+
+
+class MantisSmoothView(C.Structure):
+    _fields_ = [("n_obs", C.c_int32), ("pad", C.c_int32), ("rms", C.c_double), ("T_w_b", C.c_double * 16),
+                ("covariance", C.c_double * 36)]
+
+
 class MantisRefineRobustParams(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("loss", C.c_int32), ("tuning", C.c_double), ("scale_floor", C.c_double)]
 
@@ -314,6 +334,13 @@ _SIGS = {
                                 C.POINTER(MantisRefineParams), C.POINTER(MantisResult),
                                 C.POINTER(MantisRefineResult)]),
     "mantis_get_refine_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "mantis_default_smooth_params": (None, [C.POINTER(MantisSmoothParams)]),
+    "mantis_smooth_sizes": (None, [C.POINTER(C.c_int32)] * 3),
+    "mantis_smooth_batch": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MantisSmoothParams),
+                                      C.POINTER(MantisSmoothResult), C.POINTER(MantisSmoothView)]),
+    "mantis_get_smooth_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "mantis_get_smooth_pass": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     "mantis_default_refine_robust_params": (None, [C.c_int32, C.POINTER(MantisRefineRobustParams)]),
     "mantis_refine_robust_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mantis_refine_set_robust": (C.c_int, [C.c_void_p, C.POINTER(MantisRefineRobustParams)]),
@@ -692,6 +719,87 @@ class Mantis:
                                                  Skw.ctypes.data, rows.ctypes.data, acc.ctypes.data),
                   "get_refine_record")
         return T, codes, Sw, Skw, rows, acc
+
+    # window smoothing (mantis_smooth*, include/mantis.h) ---------------------
+    def smooth_params(self, **params):
+        """mantis_default_smooth_params, then the overrides (`lambda_` is the C field `lambda`)."""
+        p = MantisSmoothParams()
+        lib().mantis_default_smooth_params(C.byref(p))
+        for k, v in params.items():
+            if k not in dict(MantisSmoothParams._fields_) or k == "struct_size":
+                raise TypeError(f"smooth: unknown parameter {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def smooth_batch(self, images, windows, views, T_in, motions=None, prior_T=None, prior_cov=None, **params):
+        """mantis_smooth_batch: `windows` windows of `views` views (images
+        window-major, then view, then camera) from the base poses T_in
+        (windows x views x 4 x 4). motions: windows x (views - 1) x 7 =
+        delta_pos | delta_quat_xyzw (a zero quaternion: no factor on that
+        step). prior_T (windows x 4 x 4) with prior_cov (windows x 6 x 6):
+        the optional prior on view 0. Returns (results [windows],
+        views [windows][views])."""
+        n = len(images)
+        assert windows > 0 and views > 0 and n % (windows * views) == 0
+        cams = (MantisImage * n)(*images)
+        T = np.ascontiguousarray(T_in, np.float64).reshape(-1)
+        assert T.size == 16 * windows * views
+        mo = None
+        if motions is not None:
+            mo = np.ascontiguousarray(motions, np.float64).reshape(-1)
+            assert mo.size == 7 * windows * (views - 1)
+        pT = pC = None
+        if prior_T is not None:
+            pT = np.ascontiguousarray(prior_T, np.float64).reshape(-1)
+            assert pT.size == 16 * windows
+        if prior_cov is not None:
+            pC = np.ascontiguousarray(prior_cov, np.float64).reshape(-1)
+            assert pC.size == 36 * windows
+        p = self.smooth_params(**params)
+        out = (MantisSmoothResult * windows)()
+        vw = (MantisSmoothView * (windows * views))()
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        self._chk(lib().mantis_smooth_batch(self.h, cams, windows, views, n // (windows * views), T.ctypes.data, ptr(mo),
+                                            ptr(pT), ptr(pC), C.byref(p), out, vw), "smooth_batch")
+        self._smooth_shape = (views, (n // (windows * views)) * out[0].n_cand)
+        return list(out), [[vw[w * views + k] for k in range(views)] for w in range(windows)]
+
+    def smooth_record(self, window, view, pass_):
+        """mantis_get_smooth_record: refine_record's tuple for view `view` of
+        window `window`, pass `pass_` (0 .. the window's iterations_run) of
+        the last smooth call made with record=1."""
+        shape = getattr(self, "_smooth_shape", None)
+        if shape is None:
+            raise MantisError("smooth_record: no smooth call on this context")
+        ns = shape[1]
+        T = np.zeros((4, 4))
+        codes = np.zeros(ns, np.int32)
+        Sw = np.zeros(ns, np.int32)
+        Skw = np.zeros(ns, np.int32)
+        rows = np.zeros((ns, 7))
+        acc = np.zeros(28)
+        self._chk(lib().mantis_get_smooth_record(self.h, window, view, pass_, T.ctypes.data, codes.ctypes.data,
+                                                 Sw.ctypes.data, Skw.ctypes.data, rows.ctypes.data, acc.ctypes.data),
+                  "get_smooth_record")
+        return T, codes, Sw, Skw, rows, acc
+
+    def smooth_pass_record(self, window, pass_):
+        """mantis_get_smooth_pass: (e [N - 1, 6], J [N - 1, 2, 6, 6] = Ja | Jb,
+        prior_e [6], prior_J [6, 6], delta [N, 6]) of pass `pass_` of window
+        `window` of the last smooth call made with record=1."""
+        shape = getattr(self, "_smooth_shape", None)
+        if shape is None:
+            raise MantisError("smooth_pass_record: no smooth call on this context")
+        N = shape[0]
+        e = np.zeros((max(N - 1, 0), 6))
+        J = np.zeros((max(N - 1, 0), 2, 6, 6))
+        pe = np.zeros(6)
+        pJ = np.zeros((6, 6))
+        delta = np.zeros((N, 6))
+        self._chk(lib().mantis_get_smooth_pass(self.h, window, pass_, e.ctypes.data if e.size else None,
+                                               J.ctypes.data if J.size else None, pe.ctypes.data, pJ.ctypes.data,
+                                               delta.ctypes.data), "get_smooth_pass")
+        return e, J, pe, pJ, delta
 
     REFINE_LOSSES = {None: 0, "none": 0, "huber": 1, "tukey": 2}
 

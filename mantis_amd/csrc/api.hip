@@ -387,6 +387,18 @@ struct Ctx {
   } cb, ib, rb;  // extrinsic, intrinsic, rig
   // what mantis_calib_set_robust left for the three of them (loss 0 until then)
   mantis_refine_robust_params calib_robust{};
+  // window smoothing (smooth_impl.hip): its own workspaces, apart from the refinement's, grown to
+  // the largest call, and the last call's shape (mantis_get_smooth_record / _pass). out: the views'
+  // states, the windows' results and the final blocks (one copy back); in: the motions' Transforms,
+  // the priors and the cameras' inverse extrinsics; work: the chain's blocks and the pass records
+  struct Smooth {
+    uint8_t *d_out = nullptr, *h_out = nullptr, *d_in = nullptr, *h_in = nullptr;  // h: pinned
+    double* d_work = nullptr;
+    void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
+    size_t out_cap = 0, in_cap = 0, work_cap = 0, slot_cap = 0;
+    int windows = 0, N = 0, C = 0, P = 0, record = 0, cands = 0, lay_F = 0;  // the last call
+    std::vector<int32_t> runs;  // its windows' iterations_run
+  } sm;
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -1449,6 +1461,11 @@ mantis_status mantis_destroy(void* ctx) {
     if (p) (void)hipFree(p);
   if (c->rf.h_state) (void)hipHostFree(c->rf.h_state);
   if (c->rf.h_rstats) (void)hipHostFree(c->rf.h_rstats);
+  void* sptrs[] = {c->sm.d_out, c->sm.d_in, c->sm.d_work, c->sm.d_slots};
+  for (void* p : sptrs)
+    if (p) (void)hipFree(p);
+  if (c->sm.h_out) (void)hipHostFree(c->sm.h_out);
+  if (c->sm.h_in) (void)hipHostFree(c->sm.h_in);
   for (Ctx::Linecal* k : {&c->cb, &c->ib, &c->rb}) {
     void* kptrs[] = {k->d_state, k->d_T, k->d_acc, k->d_Y, k->d_Wt, k->d_cnt, k->d_pd,
                      k->d_recT, k->d_recE, k->d_recKD, k->d_recAcc, k->d_slots,
@@ -2317,6 +2334,7 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "mcl_modes_impl.hip"
 #include "mcl_color_impl.hip"
 #include "refine_impl.hip"
+#include "smooth_impl.hip"
 #include "linecal_impl.hip"
 #include "mcl_refine_impl.hip"
 #include "ros_wire.h"

@@ -25,6 +25,7 @@ static int g_jacobi_ff = 1;
 #include "mk_rpp.h"
 #include "mk_screen.h"
 #include "mk_shard.h"
+#include "mk_smooth.h"
 #include "mk_sort.h"
 #include "mk_track.h"
 
@@ -938,5 +939,115 @@ void hc_mcl_recentre(const void* modes, double g, const double* T_ref, const int
     mk::track::xf_to_mat4(X, T + 16 * (size_t)j);
   }
 }
+
+// Window smoothing (mk_smooth.h): the rules k_smooth_solve and the host's conclude run.
+// the motion's Transform as mantis_track forms it; returns 0 (and leaves D) when the motion is unset
+int hc_smooth_motion(const double* pos3, const double* quat4, double* D) {
+  if (!(quat4[0] * quat4[0] + quat4[1] * quat4[1] + quat4[2] * quat4[2] + quat4[3] * quat4[3] >= 0.5)) return 0;
+  mk::shard::quat_to_mat4(quat4, pos3, D);
+  return 1;
+}
+void hc_smooth_log(const double* R9, double* phi) { mk::smooth::log_so3(R9, phi); }
+void hc_smooth_jr_inv(const double* phi, double* J9) { mk::smooth::jr_inv(phi, J9); }
+void hc_smooth_between(const double* Tk, const double* Tk1, const double* D, double wt, double wr, double* e, double* Ja,
+                       double* Jb) {
+  mk::smooth::between(Tk, Tk1, D, wt, wr, e, Ja, Jb);
+}
+// the prior factor whitened by sigma_row L_c^-1 of cov (36); returns 0 when cov is not finite or not PD
+int hc_smooth_prior(const double* T0, const double* Tp, const double* cov, double sigma_row, double* e, double* J) {
+  double Wp[36];
+  if (!mk::smooth::prior_whitener(cov, sigma_row, Wp)) return 0;
+  mk::smooth::prior(T0, Tp, Wp, e, J);
+  return 1;
+}
+// the blocks of every view of a window from its accumulators (N x 28) and whitened factors
+void hc_smooth_assemble(int N, const double* acc28, const int32_t* has, const double* fe, const double* fJ, int has_prior,
+                        const double* pe, const double* pJ, double lambda, double* Hd, double* Ho, double* g) {
+  for (int k = 0; k < N; k++)
+    mk::smooth::assemble(k, N, acc28 + 28 * (size_t)k, has, fe, fJ, has_prior, pe, pJ, lambda, Hd + 36 * (size_t)k,
+                         Ho + 36 * (size_t)k, g + 6 * (size_t)k);
+}
+// blocks -> x = -H^-1 g (N x 6), with the factor (Ld, Lo: N x 36); -1, or the first view whose block is not PD
+int hc_smooth_solve(int N, const double* Hd, const double* Ho, const double* g, const int32_t* has, double* x, double* Ld,
+                    double* Lo) {
+  return mk::smooth::solve(N, Hd, Ho, g, has, Ld, Lo, x);
+}
+// the diagonal blocks of H^-1 (N x 36); -1, or the first view whose block is not PD
+int hc_smooth_marginals(int N, const double* Hd, const double* Ho, const int32_t* has, double* S) {
+  std::vector<double> Ld(36 * (size_t)N), Lo(36 * (size_t)N), x(6 * (size_t)N), g(6 * (size_t)N, 0.0);
+  const int bad = mk::smooth::solve(N, Hd, Ho, g.data(), has, Ld.data(), Lo.data(), x.data());
+  if (bad >= 0) return bad;
+  mk::smooth::marginals(N, Ld.data(), Lo.data(), has, S);
+  return -1;
+}
+// the figures of a pass: out = [rms, motion_rms, cost], counts = [n_obs, n_factors]
+void hc_smooth_sums(int N, const int32_t* n_obs, const double* acc28, const int32_t* has, const double* fe, int has_prior,
+                    const double* pe, double sigma_row, double* out3, int32_t* counts2) {
+  int32_t n = 0;
+  double rtr = 0;
+  for (int k = 0; k < N; k++) {
+    n += n_obs[k];
+    rtr += acc28[28 * (size_t)k + 27];
+  }
+  mk::smooth::Sums S;
+  mk::smooth::window_sums(N, n, rtr, has, fe, has_prior, pe, sigma_row, S);
+  out3[0] = S.rms;
+  out3[1] = S.motion_rms;
+  out3[2] = S.cost;
+  counts2[0] = S.n_obs;
+  counts2[1] = S.n_factors;
+}
+void hc_smooth_conclude(int N, const double* Hd, const double* Ho, const int32_t* has, int min_obs, double max_rms,
+                        mantis_smooth_result* R, mantis_smooth_view* V) {
+  mk::smooth::conclude(N, Hd, Ho, has, min_obs, max_rms, *R, V);
+}
+// The whole call of one window on host frames (frames: N x C pointers to W x H frames of stride
+// 3 W; motions: (N - 1) x 7 = delta_pos | delta_quat; prior_T / prior_cov nullable). The record
+// pointers (each nullable) get every pass taken: recT [pass][N][16], recAcc [pass][N][28], recN
+// [pass][N], recE [pass][N - 1][6], recJ [pass][N - 1][72], recPe [pass][6], recPJ [pass][36],
+// recDelta [pass][N][6]. Returns 0 when the prior covariance is refused.
+int hc_smooth_seq(int N, const double* T_in, const double* motions, const double* prior_T, const double* prior_cov,
+                  const double* Tbc, const double* K, const double* D, const uint8_t* const* frames, int C, int W, int H,
+                  const double* X, int nw, int nr, int ng, const mantis_smooth_params* p, mantis_smooth_result* out,
+                  mantis_smooth_view* views, double* recT, double* recAcc, int32_t* recN, double* recE, double* recJ,
+                  double* recPe, double* recPJ, double* recDelta) {
+  namespace rf = mk::refine;
+  namespace sm = mk::smooth;
+  const int n = nw + nr + ng;
+  std::vector<uint8_t> flags(n > 0 ? n : 1);
+  rf::line_flags(X, n, p->landmark_pitch, flags.data());
+  std::vector<int32_t> cand(n > 0 ? n : 1);
+  const int nc = rf::candidates(flags.data(), n, cand.data());
+  std::vector<mk::GnCam> gc(C);
+  std::vector<mk::Cam> cm(C);
+  for (int c = 0; c < C; c++) {
+    rf::gncam_from(Tbc + 16 * c, gc[c]);
+    cm[c] = hc_cam(K + 9 * c, D + 4 * c);
+  }
+  const int NF = N > 1 ? N - 1 : 1;
+  std::vector<double> Dm(16 * (size_t)NF, 0.0);
+  std::vector<int32_t> has(NF, 0);
+  for (int k = 0; k < N - 1; k++) has[k] = hc_smooth_motion(motions + 7 * k, motions + 7 * k + 3, &Dm[16 * (size_t)k]);
+  double Wp[36] = {0};
+  if (prior_T && !sm::prior_whitener(prior_cov, p->sigma_row, Wp)) return 0;
+  std::vector<sm::PassRecord> rec;
+  sm::smooth_seq(N, T_in, Dm.data(), has.data(), prior_T ? 1 : 0, prior_T, Wp, gc.data(), cm.data(), frames, C, W, H, X,
+                 nw, nr, cand.data(), nc, *p, *out, views, &rec);
+  for (size_t q = 0; q < rec.size(); q++) {
+    const sm::PassRecord& P = rec[q];
+    if (recT) std::memcpy(recT + q * 16 * N, P.T.data(), sizeof(double) * 16 * N);
+    if (recAcc) std::memcpy(recAcc + q * 28 * N, P.acc28.data(), sizeof(double) * 28 * N);
+    if (recN) std::memcpy(recN + q * N, P.n_obs.data(), sizeof(int32_t) * N);
+    if (recE && N > 1) std::memcpy(recE + q * 6 * (N - 1), P.e.data(), sizeof(double) * 6 * (N - 1));
+    if (recJ && N > 1) std::memcpy(recJ + q * 72 * (N - 1), P.J.data(), sizeof(double) * 72 * (N - 1));
+    if (recPe) std::memcpy(recPe + q * 6, P.pe.data(), sizeof(double) * 6);
+    if (recPJ) std::memcpy(recPJ + q * 36, P.pJ.data(), sizeof(double) * 36);
+    if (recDelta) std::memcpy(recDelta + q * 6 * N, P.delta.data(), sizeof(double) * 6 * N);
+  }
+  return 1;
+}
+int hc_sizeof_smooth_params(void) { return (int)sizeof(mantis_smooth_params); }
+int hc_sizeof_smooth_result(void) { return (int)sizeof(mantis_smooth_result); }
+int hc_sizeof_smooth_view(void) { return (int)sizeof(mantis_smooth_view); }
 
 }  // extern "C"
