@@ -123,8 +123,8 @@ __global__ __launch_bounds__(256) void k_linecal_obs(const FrameDesc* __restrict
   double Rt[9], tw[3];
   rfn::pose_parts(a.T + 16 * (size_t)rig, Rt, tw);
   const double s = 1.0 / cm.fx;
-  const int R = a.win.R, k = l - R;
-  const bool active = l <= 2 * R;
+  const int k = l - a.win.R;
+  const bool active = l <= 2 * a.win.R;
   Slot* out = (Slot*)a.slots + (size_t)pass * a.pass_slots + (size_t)f * a.n_cand;
   const int c0 = chunk * kRefineCands, c1 = min(c0 + kRefineCands, a.n_cand);
   for (int base = c0 + wave * 2; base < c1; base += 8) {  // wave-uniform trips: every lane reaches the shuffles
@@ -138,23 +138,9 @@ __global__ __launch_bounds__(256) void k_linecal_obs(const FrameDesc* __restrict
     int gcode;
     if constexpr (P::kExt) gcode = cal::geom(Rt, tw, gc, lmk.xyz + 3 * i, axis, free_ext, g);
     else gcode = rfn::geom(Rt, tw, gc, lmk.xyz + 3 * i, axis, g.g);
-    int x = 0, y = 0;
-    int outside = 0;
-    if (!gcode && active) outside = rfn::sample_px(cm, g.g, k, s, W, H, &x, &y, nullptr, nullptr) ? 0 : 1;
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) outside |= __shfl_xor(outside, m, 32);
-    int32_t w = 0;
-    if (!gcode && active && !outside) {  // 0 <= x < W, 0 <= y < H: the pixel is inside the frame
-      const uint32_t pv = load_bgr(bgr, y * W + x, npx);
-      w = rfn::px_weight((int)(pv & 0xffu), (int)((pv >> 8) & 0xffu), (int)((pv >> 16) & 0xffu), tg, a.win.white_thresh);
-    }
-    int32_t Sw = w, Skw = k * w;
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) {
-      Sw += __shfl_xor(Sw, m, 32);
-      Skw += __shfl_xor(Skw, m, 32);
-    }
-    const int32_t w_lo = __shfl(w, 0, 32), w_hi = __shfl(w, 2 * R, 32);
+    int outside;
+    int32_t Sw, Skw, w_lo, w_hi;
+    refine_window(cm, bgr, W, H, npx, tg, g.g, gcode, s, k, active, a.win, outside, Sw, Skw, w_lo, w_hi);
     if (l == 0 && live) {
       rfn::Slot o7;
       rfn::finish(gcode, outside != 0, w_lo, w_hi, Sw, Skw, a.win.min_weight, s, g.g, o7);
@@ -236,7 +222,8 @@ __global__ __launch_bounds__(256) void k_linecal_hist(LinecalArgs a, int pass) {
 // kernel's loops on row r times sq[r - k0], its sqrt(w) -- the same kU trips'
 // loads in flight before their MFMAs, the same accumulation order; trips past
 // the end add exact zeros. lh and hh: the 21-column row only. (The plain
-// kernel keeps its own copy of the loops so that its code stays what it was.)
+// kernel keeps its own copy of the loops: run through these helpers, its
+// 21-column instantiation measured 1.5 % slower)
 template <class P>
 __device__ __forceinline__ void linecal_trips(const typename P::Slot* sl, const double* sq, int k0, int k1, int kk,
                                               int m, v4d& ll, v4d& lh, v4d& hh) {
@@ -339,7 +326,7 @@ __global__ __launch_bounds__(256) void k_linecal_rig(LinecalArgs a, int pass) {
   if (a.st->done) return;
   const int C = a.C, nc = a.n_cand, nS = a.l.nS;
   const int kk = lane >> 4, m = lane & 15;
-  if constexpr (!kR) {  // the loops as they were before the robust rows: this instantiation keeps its code
+  if constexpr (!kR) {  // the plain loops, spelled out (see linecal_trips)
     for (int cam = wave; cam < C; cam += 4) {  // wave-uniform
       const Slot* sl = (const Slot*)a.slots + (size_t)pass * a.pass_slots + (size_t)(rig * C + cam) * nc;
       double* sa = s_acc + P::kAcc * cam;
@@ -761,10 +748,7 @@ constexpr LinecalNames kIcalibNames{"icalib", "intrinsic calibration", "icalib_o
 constexpr LinecalNames kRcalibNames{"rcalib", "rig calibration", "rcalib_obs/k_rcalib_obs", "rcalib_rig/k_rcalib_rig",
                                     "rcalib_solve/k_rcalib_solve", "rcalib_hist/k_rcalib_hist"};
 
-mantis_status linecal_fail(Ctx* c, const LinecalNames& nm, const char* what) {
-  c->err = std::string(nm.prefix) + ": " + what;
-  return MANTIS_ERR_ARG;
-}
+mantis_status linecal_fail(Ctx* c, const LinecalNames& nm, const char* what) { return line_fail(c, nm.prefix, what); }
 
 // workspaces for a call of N views x C cameras; robust: the switch is on
 template <class P>
@@ -1000,17 +984,7 @@ mantis_status linecal_record(Ctx* c, const Ctx::Linecal& k, const LinecalNames& 
     HIP_OK(hipMemcpy(KD, k.d_recKD + (size_t)pass * k.C * lc::kPi, sizeof(double) * lc::kPi * k.C, hipMemcpyDeviceToHost));
   if (acc)
     HIP_OK(hipMemcpy(acc, k.d_recAcc + pr * k.C * P::kAcc, sizeof(double) * P::kAcc * k.C, hipMemcpyDeviceToHost));
-  if ((codes || Sw || Skw || rows) && ns > 0) {
-    std::vector<Slot> hs(ns);
-    HIP_OK(hipMemcpy(hs.data(), (const Slot*)k.d_slots + pr * ns, sizeof(Slot) * ns, hipMemcpyDeviceToHost));
-    for (size_t q = 0; q < ns; q++) {
-      if (codes) codes[q] = hs[q].code;
-      if (Sw) Sw[q] = hs[q].Sw;
-      if (Skw) Skw[q] = hs[q].Skw;
-      if (rows) std::memcpy(rows + P::kRow * q, hs[q].row, sizeof(double) * P::kRow);
-    }
-  }
-  return MANTIS_OK;
+  return slots_scatter<Slot, P::kRow>(c, (const Slot*)k.d_slots + pr * ns, ns, codes, Sw, Skw, rows);
 }
 
 // ---- the three entry points: each its own validation, then the one driver ----

@@ -45,6 +45,39 @@ struct RefineArgs {
 
 constexpr int kRefineCands = 32;  // candidates of a k_refine_obs block: 4 trips of 4 waves x 2
 
+// One candidate's window in one 32-lane half, at the geometry g (gcode: what
+// rfn::geom returned; tg: the landmark's target colour; npx = W H). Lane
+// l <= 2 R of the half (active) is sample k = l - R, with one distort and one
+// pixel load; the caller forms k and active once, before its candidate loop.
+// The outside vote, Sw and Skw are integer sums by __shfl_xor inside the half,
+// w_lo and w_hi the weights of the window's two ends; all five come back in
+// every lane of the half. Every lane of the wave executes the shuffles: call
+// it outside any lane-divergent branch.
+__device__ __forceinline__ void refine_window(const Cam& cm, const uint8_t* bgr, int W, int H, int npx, const int* tg,
+                                              const rfn::Geom& g, int gcode, double s, int k, bool active,
+                                              const rfn::Window& win, int& outside, int32_t& Sw, int32_t& Skw,
+                                              int32_t& w_lo, int32_t& w_hi) {
+  int x = 0, y = 0;
+  outside = 0;
+  if (!gcode && active) outside = rfn::sample_px(cm, g, k, s, W, H, &x, &y, nullptr, nullptr) ? 0 : 1;
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) outside |= __shfl_xor(outside, m, 32);
+  int32_t w = 0;
+  if (!gcode && active && !outside) {  // 0 <= x < W, 0 <= y < H: the pixel is inside the frame
+    const uint32_t pv = load_bgr(bgr, y * W + x, npx);
+    w = rfn::px_weight((int)(pv & 0xffu), (int)((pv >> 8) & 0xffu), (int)((pv >> 16) & 0xffu), tg, win.white_thresh);
+  }
+  Sw = w;
+  Skw = k * w;
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) {
+    Sw += __shfl_xor(Sw, m, 32);
+    Skw += __shfl_xor(Skw, m, 32);
+  }
+  w_lo = __shfl(w, 0, 32);
+  w_hi = __shfl(w, 2 * win.R, 32);
+}
+
 // Block (candidate chunk, camera, rig): each wave takes two candidates at a
 // time, one per 32-lane half; lane l <= 2 R of a half is sample k = l - R. The
 // pose and the camera come from the grid and the kernel arguments (rig_stride:
@@ -68,8 +101,8 @@ __global__ __launch_bounds__(256) void k_refine_obs(const FrameDesc* __restrict_
   double Rt[9], tw[3];
   rfn::pose_parts(S.res.T_w_b, Rt, tw);
   const double s = 1.0 / cm.fx;
-  const int R = a.win.R, k = l - R;
-  const bool active = l <= 2 * R;
+  const int k = l - a.win.R;
+  const bool active = l <= 2 * a.win.R;
   rfn::Slot* out = a.slots + (size_t)pass * a.pass_slots + (size_t)(rig * a.C + cam) * a.n_cand;
   const int c0 = chunk * kRefineCands, c1 = min(c0 + kRefineCands, a.n_cand);
   for (int base = c0 + wave * 2; base < c1; base += 8) {  // wave-uniform trips: every lane reaches the shuffles
@@ -81,23 +114,9 @@ __global__ __launch_bounds__(256) void k_refine_obs(const FrameDesc* __restrict_
     rfn::target_bgr(i, lmk.nw, lmk.nr, tg);
     rfn::Geom g;
     const int gcode = rfn::geom(Rt, tw, gc, lmk.xyz + 3 * i, axis, g);
-    int x = 0, y = 0;
-    int outside = 0;
-    if (!gcode && active) outside = rfn::sample_px(cm, g, k, s, W, H, &x, &y, nullptr, nullptr) ? 0 : 1;
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) outside |= __shfl_xor(outside, m, 32);
-    int32_t w = 0;
-    if (!gcode && active && !outside) {  // 0 <= x < W, 0 <= y < H: the pixel is inside the frame
-      const uint32_t pv = load_bgr(bgr, y * W + x, npx);
-      w = rfn::px_weight((int)(pv & 0xffu), (int)((pv >> 8) & 0xffu), (int)((pv >> 16) & 0xffu), tg, a.win.white_thresh);
-    }
-    int32_t Sw = w, Skw = k * w;
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) {
-      Sw += __shfl_xor(Sw, m, 32);
-      Skw += __shfl_xor(Skw, m, 32);
-    }
-    const int32_t w_lo = __shfl(w, 0, 32), w_hi = __shfl(w, 2 * R, 32);
+    int outside;
+    int32_t Sw, Skw, w_lo, w_hi;
+    refine_window(cm, bgr, W, H, npx, tg, g, gcode, s, k, active, a.win, outside, Sw, Skw, w_lo, w_hi);
     if (l == 0 && live) {
       rfn::Slot o;
       rfn::finish(gcode, outside != 0, w_lo, w_hi, Sw, Skw, a.win.min_weight, s, g, o);
@@ -106,11 +125,63 @@ __global__ __launch_bounds__(256) void k_refine_obs(const FrameDesc* __restrict_
   }
 }
 
-// One block per rig: the four waves build M^T M of M = [J | r] over the rig's
-// C n_cand slots with v_mfma_f64_16x16x4f64, four rows per instruction, summed
-// over the waves in wave order (as gn_acc_block); n_obs is a block count;
-// thread 0 ends the pass (rfn::end_pass: gates, gn_solve6, T_k+1) and writes
-// the pass record. Pass I solves nothing.
+// The 7-column accumulation of the step kernels (k_refine_step,
+// k_refine_step_robust, k_smooth_acc): one block of four waves per rig builds
+// M^T M of M = [J | r] over the rig's slots with v_mfma_f64_16x16x4f64, four
+// rows per instruction (the tile's entry (i, j) is in lane (i & 3) * 16 + j,
+// register i >> 2), and sums the waves' tiles in wave order (as gn_acc_block).
+//
+// One wave's trips over the n rows of the slots sl, kk = lane >> 4 and
+// m = lane & 15: eight trips' loads in flight before their MFMAs (a loop of one
+// trip waited for one 72-byte-strided load per MFMA); trips past the end add
+// exact zeros. kW: row r times sqw[r], its sqrt(w), from LDS.
+template <bool kW>
+__device__ __forceinline__ void refine_trips(const rfn::Slot* sl, const double* sqw, int n, int wave, int kk, int m,
+                                             v4d& acc) {
+  constexpr int kU = 8;
+  for (int base = wave * 4; base < n; base += 16 * kU) {
+    double v[kU];
+#pragma unroll
+    for (int u = 0; u < kU; u++) {
+      const int r = base + 16 * u + kk;
+      if constexpr (kW) v[u] = (r < n && m < 7) ? sl[r].row[m] * sqw[r] : 0.0;
+      else v[u] = (r < n && m < 7) ? sl[r].row[m] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < kU; u++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v[u], v[u], acc, 0, 0, 0);
+  }
+}
+// the code-0 rows the block's threads count among `rows` slots, summed over the wave (in every lane)
+__device__ __forceinline__ int32_t refine_count(const rfn::Slot* sl, int rows, int t) {
+  int32_t n = 0;
+  for (int r = t; r < rows; r += 256) n += sl[r].code == 0;
+#pragma unroll
+  for (int q = 32; q >= 1; q >>= 1) n += __shfl_xor(n, q, 64);
+  return n;
+}
+// a wave's tile into red; after the block's barrier one thread sums the four tiles into acc28
+__device__ __forceinline__ void refine_tile(double (*red)[16][16], int wave, int kk, int m, const v4d& acc) {
+  for (int r = 0; r < 4; r++) red[wave][kk + 4 * r][m] = acc[r];
+}
+__device__ __forceinline__ void refine_sum28(const double (*red)[16][16], double* acc28) {
+  int e = 0;
+  for (int i = 0; i < 6; i++)
+    for (int j = i; j < 6; j++) acc28[e++] = red[0][i][j] + red[1][i][j] + red[2][i][j] + red[3][i][j];
+  for (int i = 0; i < 6; i++) acc28[21 + i] = red[0][i][6] + red[1][i][6] + red[2][i][6] + red[3][i][6];
+  acc28[27] = red[0][6][6] + red[1][6][6] + red[2][6][6] + red[3][6][6];
+}
+// the pass record of a rig: the pose the pass observed at and its acc28, also kept in the rig's state
+__device__ __forceinline__ void refine_record(const RefineArgs& a, RefineRig& S, int rig, int pass,
+                                              const double* acc28) {
+  double* rT = a.recT + ((size_t)pass * a.n_rigs + rig) * 16;
+  double* rA = a.recAcc + ((size_t)pass * a.n_rigs + rig) * 28;
+  for (int i = 0; i < 16; i++) rT[i] = S.res.T_w_b[i];
+  for (int i = 0; i < 28; i++) rA[i] = S.acc28[i] = acc28[i];
+}
+
+// One block per rig: the accumulation above over the rig's C n_cand slots;
+// n_obs is a block count; thread 0 ends the pass (rfn::end_pass: gates,
+// gn_solve6, T_k+1) and writes the pass record. Pass I solves nothing.
 __global__ __launch_bounds__(256) void k_refine_step(RefineArgs a, int pass) {
   __shared__ double red[4][16][16];
   __shared__ int32_t cnt[4];
@@ -121,39 +192,16 @@ __global__ __launch_bounds__(256) void k_refine_step(RefineArgs a, int pass) {
   const rfn::Slot* sl = a.slots + (size_t)pass * a.pass_slots + (size_t)rig * rows;
   v4d acc = {0, 0, 0, 0};
   const int kk = lane >> 4, m = lane & 15;
-  // eight trips' loads in flight before their MFMAs (the accumulation order is
-  // the plain loop's; trips past the end add exact zeros): the plain loop waited
-  // for one 72-byte-strided load per MFMA
-  constexpr int kU = 8;
-  for (int base = wave * 4; base < rows; base += 16 * kU) {
-    double v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; u++) {
-      const int r = base + 16 * u + kk;
-      v[u] = (r < rows && m < 7) ? sl[r].row[m] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kU; u++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v[u], v[u], acc, 0, 0, 0);
-  }
-  int32_t n = 0;
-  for (int r = t; r < rows; r += 256) n += sl[r].code == 0;
-#pragma unroll
-  for (int q = 32; q >= 1; q >>= 1) n += __shfl_xor(n, q, 64);
+  refine_trips<false>(sl, nullptr, rows, wave, kk, m, acc);
+  const int32_t n = refine_count(sl, rows, t);
   if (lane == 0) cnt[wave] = n;
-  for (int r = 0; r < 4; r++) red[wave][(lane >> 4) + 4 * r][lane & 15] = acc[r];
+  refine_tile(red, wave, kk, m, acc);
   __syncthreads();
   if (t == 0) {
     double acc28[28];
-    int e = 0;
-    for (int i = 0; i < 6; i++)
-      for (int j = i; j < 6; j++) acc28[e++] = red[0][i][j] + red[1][i][j] + red[2][i][j] + red[3][i][j];
-    for (int i = 0; i < 6; i++) acc28[21 + i] = red[0][i][6] + red[1][i][6] + red[2][i][6] + red[3][i][6];
-    acc28[27] = red[0][6][6] + red[1][6][6] + red[2][6][6] + red[3][6][6];
+    refine_sum28(red, acc28);
     const int32_t n_obs = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-    double* rT = a.recT + ((size_t)pass * a.n_rigs + rig) * 16;
-    double* rA = a.recAcc + ((size_t)pass * a.n_rigs + rig) * 28;
-    for (int i = 0; i < 16; i++) rT[i] = S.res.T_w_b[i];
-    for (int i = 0; i < 28; i++) rA[i] = S.acc28[i] = acc28[i];
+    refine_record(a, S, rig, pass, acc28);
     S.done = rfn::end_pass(acc28, n_obs, pass, a.I, a.min_obs, a.lambda, S.res) ? 1 : 0;
   }
 }
@@ -166,9 +214,27 @@ namespace {
 
 namespace rfn = mk::refine;
 
-mantis_status refine_fail(Ctx* c, const char* what) {
-  c->err = std::string("refine: ") + what;
+// an argument error of the entry point that calls itself `prefix`
+mantis_status line_fail(Ctx* c, const char* prefix, const char* what) {
+  c->err = std::string(prefix) + ": " + what;
   return MANTIS_ERR_ARG;
+}
+mantis_status refine_fail(Ctx* c, const char* what) { return line_fail(c, "refine", what); }
+
+// ns slots (S: rfn::Slot or a calibration's, rows of kRow doubles) from the device into the caller's arrays
+template <class S, int kRow>
+mantis_status slots_scatter(Ctx* c, const S* d_slots, size_t ns, int32_t* codes, int32_t* Sw, int32_t* Skw,
+                            double* rows) {
+  if (!(codes || Sw || Skw || rows) || ns == 0) return MANTIS_OK;
+  std::vector<S> hs(ns);
+  HIP_OK(hipMemcpy(hs.data(), d_slots, sizeof(S) * ns, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < ns; k++) {
+    if (codes) codes[k] = hs[k].code;
+    if (Sw) Sw[k] = hs[k].Sw;
+    if (Skw) Skw[k] = hs[k].Skw;
+    if (rows) std::memcpy(rows + kRow * k, hs[k].row, sizeof(double) * kRow);
+  }
+  return MANTIS_OK;
 }
 
 template <class T>
@@ -242,6 +308,37 @@ mantis_status refine_workspace(Ctx* c, int R, int C, int F, int I, bool record, 
   return MANTIS_OK;
 }
 
+// The checks every solver on the grid lines shares, in the order its errors
+// fire: the window and solve fields (Pm: mantis_refine_params or
+// mantis_smooth_params, which name them alike), then, behind the caller's own
+// fields, the record flag and the n frames (cams: not null).
+template <class Pm>
+mantis_status line_check_fields(Ctx* c, const char* prefix, const Pm* p) {
+  if (p->iterations < 0 || p->iterations > rfn::kMaxIterations) return line_fail(c, prefix, "iterations outside 0..10");
+  if (p->half_window < 1 || p->half_window > rfn::kMaxHalfWindow)
+    return line_fail(c, prefix, "half_window outside 1..15");
+  if (p->white_thresh < 1 || p->white_thresh > 195075) return line_fail(c, prefix, "white_thresh outside 1..195075");
+  if (p->min_weight < 1) return line_fail(c, prefix, "min_weight must be >= 1");
+  if (p->min_obs < 6) return line_fail(c, prefix, "min_obs must be >= 6");
+  if (!(p->lambda >= 0) || !std::isfinite(p->lambda)) return line_fail(c, prefix, "lambda must be finite and >= 0");
+  if (!(p->landmark_pitch > 0) || !std::isfinite(p->landmark_pitch))
+    return line_fail(c, prefix, "landmark_pitch must be finite and > 0");
+  if (std::isnan(p->max_rms)) return line_fail(c, prefix, "max_rms is NaN");
+  return MANTIS_OK;
+}
+mantis_status line_check_frames(Ctx* c, const char* prefix, int32_t record, const mantis_image* cams, int n) {
+  if (record != 0 && record != 1) return line_fail(c, prefix, "record must be 0 or 1");
+  for (int i = 0; i < n; i++) {
+    if (cams[i].width != cams[0].width || cams[i].height != cams[0].height)
+      return line_fail(c, prefix, "all frames of a call must share one size");
+    if (!cams[i].bgr || cams[i].step_bytes < 3 * cams[i].width)
+      return line_fail(c, prefix, "bgr8 image with step >= 3*width required");
+  }
+  if (cams[0].width <= 2 || cams[0].height <= 2 || cams[0].width > c->Wmax || cams[0].height > c->Hmax)
+    return line_fail(c, prefix, "image size outside [3, max]");
+  return MANTIS_OK;
+}
+
 // the parameter and frame checks of a call of n_rigs x C frames (cams, p: not null)
 mantis_status refine_check(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32_t C, const mantis_refine_params* p) {
   if (p->struct_size != (int32_t)sizeof(mantis_refine_params)) return refine_fail(c, "params.struct_size mismatch");
@@ -249,27 +346,8 @@ mantis_status refine_check(Ctx* c, const mantis_image* cams, int32_t n_rigs, int
   if (n_rigs <= 0 || C <= 0) return refine_fail(c, "n_rigs and cams_per_rig must be positive");
   if (C > rfn::kMaxCams) return refine_fail(c, "cams_per_rig exceeds 8");
   if ((int64_t)n_rigs * C > c->F) return refine_fail(c, "n_rigs x cams_per_rig exceeds max_cams");
-  const int I = p->iterations;
-  if (I < 0 || I > rfn::kMaxIterations) return refine_fail(c, "iterations outside 0..10");
-  if (p->half_window < 1 || p->half_window > rfn::kMaxHalfWindow) return refine_fail(c, "half_window outside 1..15");
-  if (p->white_thresh < 1 || p->white_thresh > 195075) return refine_fail(c, "white_thresh outside 1..195075");
-  if (p->min_weight < 1) return refine_fail(c, "min_weight must be >= 1");
-  if (p->min_obs < 6) return refine_fail(c, "min_obs must be >= 6");
-  if (!(p->lambda >= 0) || !std::isfinite(p->lambda)) return refine_fail(c, "lambda must be finite and >= 0");
-  if (!(p->landmark_pitch > 0) || !std::isfinite(p->landmark_pitch))
-    return refine_fail(c, "landmark_pitch must be finite and > 0");
-  if (std::isnan(p->max_rms)) return refine_fail(c, "max_rms is NaN");
-  if (p->record != 0 && p->record != 1) return refine_fail(c, "record must be 0 or 1");
-  const int n = n_rigs * C;
-  for (int i = 0; i < n; i++) {
-    if (cams[i].width != cams[0].width || cams[i].height != cams[0].height)
-      return refine_fail(c, "all frames of a call must share one size");
-    if (!cams[i].bgr || cams[i].step_bytes < 3 * cams[i].width)
-      return refine_fail(c, "bgr8 image with step >= 3*width required");
-  }
-  if (cams[0].width <= 2 || cams[0].height <= 2 || cams[0].width > c->Wmax || cams[0].height > c->Hmax)
-    return refine_fail(c, "image size outside [3, max]");
-  return MANTIS_OK;
+  if (mantis_status e = line_check_fields(c, "refine", p)) return e;
+  return line_check_frames(c, "refine", p->record, cams, n_rigs * C);
 }
 
 // The device work of a checked call: n_rigs rigs of C cameras from T_in. Rig r
@@ -485,18 +563,8 @@ mantis_status mantis_get_refine_record(void* ctx, int32_t rig, int32_t pass, dou
     HIP_OK(hipMemcpy(T_w_b, r.d_recT + ((size_t)pass * r.rigs + rig) * 16, sizeof(double) * 16, hipMemcpyDeviceToHost));
   if (acc28)
     HIP_OK(hipMemcpy(acc28, r.d_recAcc + ((size_t)pass * r.rigs + rig) * 28, sizeof(double) * 28, hipMemcpyDeviceToHost));
-  if ((codes || Sw || Skw || rows) && ns > 0) {
-    std::vector<rfn::Slot> hs(ns);
-    HIP_OK(hipMemcpy(hs.data(), (const rfn::Slot*)r.d_slots + ((size_t)pass * r.rigs + rig) * ns, sizeof(rfn::Slot) * ns,
-                     hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < ns; k++) {
-      if (codes) codes[k] = hs[k].code;
-      if (Sw) Sw[k] = hs[k].Sw;
-      if (Skw) Skw[k] = hs[k].Skw;
-      if (rows) std::memcpy(rows + 7 * k, hs[k].row, sizeof(double) * 7);
-    }
-  }
-  return MANTIS_OK;
+  return slots_scatter<rfn::Slot, 7>(c, (const rfn::Slot*)r.d_slots + ((size_t)pass * r.rigs + rig) * ns, ns, codes, Sw,
+                                     Skw, rows);
 }
 
 void mantis_default_refine_robust_params(int32_t loss, mantis_refine_robust_params* p) {

@@ -68,7 +68,7 @@ __device__ uint32_t robust_select(const uint32_t* hist, uint32_t rank, uint32_t*
 //     (one 64-bit division and one trip to memory per slot instead of three);
 //     slots past them -- an eight-camera rig on the full map has 4320 -- are
 //     read again.
-//  2. Accumulation: k_refine_step's loop on row[m] * sqrt(w). The weights of
+//  2. Accumulation: refine_trips on row[m] * sqrt(w). The weights of
 //     2048 rows at a time are formed by the whole block (one row per thread
 //     and trip, so the 64-bit division, the FP64 division and the root are
 //     paid once per row, not once per MFMA lane) and wait in LDS for the 16
@@ -141,7 +141,6 @@ __global__ __launch_bounds__(256) void k_refine_step_robust(RefineArgs a, Robust
   double* rw = b.weights ? b.weights + ((size_t)pass * a.n_rigs + rig) * rows : nullptr;
   v4d acc = {0, 0, 0, 0};
   const int kk = lane >> 4, m = lane & 15;
-  constexpr int kU = 8;
   int32_t n_down = 0, n_zero = 0;
   double sum_w = 0.0;
   for (int c0 = 0; c0 < rows; c0 += kRobustChunk) {
@@ -164,16 +163,7 @@ __global__ __launch_bounds__(256) void k_refine_step_robust(RefineArgs a, Robust
       }
     }
     __syncthreads();
-    for (int base = c0 + wave * 4; base < c1; base += 16 * kU) {
-      double v[kU];
-#pragma unroll
-      for (int u = 0; u < kU; u++) {
-        const int r = base + 16 * u + kk;
-        v[u] = (r < c1 && m < 7) ? sl[r].row[m] * sqw[r - c0] : 0.0;  // r < c1 <= c0 + 2048: inside sqw
-      }
-#pragma unroll
-      for (int u = 0; u < kU; u++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v[u], v[u], acc, 0, 0, 0);
-    }
+    refine_trips<true>(sl + c0, sqw, c1 - c0, wave, kk, m, acc);  // c1 - c0 <= 2048: inside sqw
     __syncthreads();  // the next chunk overwrites sqw
   }
 #pragma unroll
@@ -187,17 +177,13 @@ __global__ __launch_bounds__(256) void k_refine_step_robust(RefineArgs a, Robust
     cnt[wave][2] = n_zero;
     wred[wave] = sum_w;
   }
-  for (int r = 0; r < 4; r++) red[wave][(lane >> 4) + 4 * r][lane & 15] = acc[r];
+  refine_tile(red, wave, kk, m, acc);
   __syncthreads();
 
   // 3. the tail
   if (t == 0) {
     double acc28[28];
-    int e = 0;
-    for (int i = 0; i < 6; i++)
-      for (int j = i; j < 6; j++) acc28[e++] = red[0][i][j] + red[1][i][j] + red[2][i][j] + red[3][i][j];
-    for (int i = 0; i < 6; i++) acc28[21 + i] = red[0][i][6] + red[1][i][6] + red[2][i][6] + red[3][i][6];
-    acc28[27] = red[0][6][6] + red[1][6][6] + red[2][6][6] + red[3][6][6];
+    refine_sum28(red, acc28);
     const int32_t down = cnt[0][1] + cnt[1][1] + cnt[2][1] + cnt[3][1];
     const int32_t zero = cnt[0][2] + cnt[1][2] + cnt[2][2] + cnt[3][2];
     mantis_refine_robust_stats& st = b.stats[rig];
@@ -206,10 +192,7 @@ __global__ __launch_bounds__(256) void k_refine_step_robust(RefineArgs a, Robust
     st.n_zero[pass] = zero;
     st.scale[pass] = sigma;
     st.sum_w[pass] = wred[0] + wred[1] + wred[2] + wred[3];
-    double* rT = a.recT + ((size_t)pass * a.n_rigs + rig) * 16;
-    double* rA = a.recAcc + ((size_t)pass * a.n_rigs + rig) * 28;
-    for (int i = 0; i < 16; i++) rT[i] = S.res.T_w_b[i];
-    for (int i = 0; i < 28; i++) rA[i] = S.acc28[i] = acc28[i];
+    refine_record(a, S, rig, pass, acc28);
     S.done = rfn::end_pass_robust(acc28, n_obs, n_obs - zero, pass, a.I, a.min_obs, a.lambda, S.res) ? 1 : 0;
   }
 }

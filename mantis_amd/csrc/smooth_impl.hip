@@ -42,11 +42,9 @@ struct SmoothArgs {
   smo::Weights w;
 };
 
-// One block per view: k_refine_step's accumulation, loop for loop (four waves,
-// eight trips' loads in flight, the wave-order sum, the block count of code-0
-// rows), without its solve. Its own copy so that k_refine_step's text, and with
-// it its code object, stays as it is. Thread 0 writes acc28, n_obs and rms of
-// the view and the pass record.
+// One block per view: k_refine_step's accumulation (refine_trips, the block
+// count of code-0 rows, the wave-order sum) without its solve. Thread 0 writes
+// acc28, n_obs and rms of the view and the pass record.
 __global__ __launch_bounds__(256) void k_smooth_acc(RefineArgs a, int pass) {
   __shared__ double red[4][16][16];
   __shared__ int32_t cnt[4];
@@ -57,36 +55,16 @@ __global__ __launch_bounds__(256) void k_smooth_acc(RefineArgs a, int pass) {
   const rfn::Slot* sl = a.slots + (size_t)pass * a.pass_slots + (size_t)rig * rows;
   v4d acc = {0, 0, 0, 0};
   const int kk = lane >> 4, m = lane & 15;
-  constexpr int kU = 8;
-  for (int base = wave * 4; base < rows; base += 16 * kU) {
-    double v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; u++) {
-      const int r = base + 16 * u + kk;
-      v[u] = (r < rows && m < 7) ? sl[r].row[m] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kU; u++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v[u], v[u], acc, 0, 0, 0);
-  }
-  int32_t n = 0;
-  for (int r = t; r < rows; r += 256) n += sl[r].code == 0;
-#pragma unroll
-  for (int q = 32; q >= 1; q >>= 1) n += __shfl_xor(n, q, 64);
+  refine_trips<false>(sl, nullptr, rows, wave, kk, m, acc);
+  const int32_t n = refine_count(sl, rows, t);
   if (lane == 0) cnt[wave] = n;
-  for (int r = 0; r < 4; r++) red[wave][(lane >> 4) + 4 * r][lane & 15] = acc[r];
+  refine_tile(red, wave, kk, m, acc);
   __syncthreads();
   if (t == 0) {
     double acc28[28];
-    int e = 0;
-    for (int i = 0; i < 6; i++)
-      for (int j = i; j < 6; j++) acc28[e++] = red[0][i][j] + red[1][i][j] + red[2][i][j] + red[3][i][j];
-    for (int i = 0; i < 6; i++) acc28[21 + i] = red[0][i][6] + red[1][i][6] + red[2][i][6] + red[3][i][6];
-    acc28[27] = red[0][6][6] + red[1][6][6] + red[2][6][6] + red[3][6][6];
+    refine_sum28(red, acc28);
     const int32_t n_obs = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-    double* rT = a.recT + ((size_t)pass * a.n_rigs + rig) * 16;
-    double* rA = a.recAcc + ((size_t)pass * a.n_rigs + rig) * 28;
-    for (int i = 0; i < 16; i++) rT[i] = S.res.T_w_b[i];
-    for (int i = 0; i < 28; i++) rA[i] = S.acc28[i] = acc28[i];
+    refine_record(a, S, rig, pass, acc28);
     S.res.n_obs[pass] = n_obs;
     S.res.rms[pass] = n_obs > 0 ? sqrt(acc28[27] / (double)n_obs) : 0.0;
     S.res.iterations_run = pass;  // the last pass taken: where the view's final figures are
@@ -282,10 +260,7 @@ namespace {
 
 namespace smo = mk::smooth;
 
-mantis_status smooth_fail(Ctx* c, const char* what) {
-  c->err = std::string("smooth: ") + what;
-  return MANTIS_ERR_ARG;
-}
+mantis_status smooth_fail(Ctx* c, const char* what) { return line_fail(c, "smooth", what); }
 
 // the device buffers of a call of Wn windows x N views, F frames, P = I + 1 passes
 struct SmoothLayout {
@@ -360,29 +335,11 @@ mantis_status smooth_check(Ctx* c, const mantis_image* cams, int32_t Wn, int32_t
   if (N > smo::kMaxViews) return smooth_fail(c, "n_views exceeds 256");
   if (C > rfn::kMaxCams) return smooth_fail(c, "cams_per_rig exceeds 8");
   if ((int64_t)Wn * N * C > c->F) return smooth_fail(c, "n_windows x n_views x cams_per_rig exceeds max_cams");
-  if (p->iterations < 0 || p->iterations > smo::kMaxIterations) return smooth_fail(c, "iterations outside 0..10");
-  if (p->half_window < 1 || p->half_window > rfn::kMaxHalfWindow) return smooth_fail(c, "half_window outside 1..15");
-  if (p->white_thresh < 1 || p->white_thresh > 195075) return smooth_fail(c, "white_thresh outside 1..195075");
-  if (p->min_weight < 1) return smooth_fail(c, "min_weight must be >= 1");
-  if (p->min_obs < 6) return smooth_fail(c, "min_obs must be >= 6");
-  if (!(p->lambda >= 0) || !std::isfinite(p->lambda)) return smooth_fail(c, "lambda must be finite and >= 0");
-  if (!(p->landmark_pitch > 0) || !std::isfinite(p->landmark_pitch))
-    return smooth_fail(c, "landmark_pitch must be finite and > 0");
-  if (std::isnan(p->max_rms)) return smooth_fail(c, "max_rms is NaN");
+  if (mantis_status e = line_check_fields(c, "smooth", p)) return e;
   if (!(p->sigma_row > 0) || !std::isfinite(p->sigma_row)) return smooth_fail(c, "sigma_row must be finite and > 0");
   if (!(p->sigma_t > 0) || !std::isfinite(p->sigma_t)) return smooth_fail(c, "sigma_t must be finite and > 0");
   if (!(p->sigma_rot > 0) || !std::isfinite(p->sigma_rot)) return smooth_fail(c, "sigma_rot must be finite and > 0");
-  if (p->record != 0 && p->record != 1) return smooth_fail(c, "record must be 0 or 1");
-  const int n = Wn * N * C;
-  for (int i = 0; i < n; i++) {
-    if (cams[i].width != cams[0].width || cams[i].height != cams[0].height)
-      return smooth_fail(c, "all frames of a call must share one size");
-    if (!cams[i].bgr || cams[i].step_bytes < 3 * cams[i].width)
-      return smooth_fail(c, "bgr8 image with step >= 3*width required");
-  }
-  if (cams[0].width <= 2 || cams[0].height <= 2 || cams[0].width > c->Wmax || cams[0].height > c->Hmax)
-    return smooth_fail(c, "image size outside [3, max]");
-  return MANTIS_OK;
+  return line_check_frames(c, "smooth", p->record, cams, Wn * N * C);
 }
 
 mantis_status smooth_impl(Ctx* c, const mantis_image* cams, int32_t Wn, int32_t N, int32_t C, const double* T_in,
@@ -600,18 +557,8 @@ mantis_status mantis_get_smooth_record(void* ctx, int32_t window, int32_t view, 
   if (acc28)
     HIP_OK(hipMemcpy(acc28, r.d_work + L.w_recAcc + ((size_t)pass * V + v) * 28, sizeof(double) * 28,
                      hipMemcpyDeviceToHost));
-  if ((codes || Sw || Skw || rows) && ns > 0) {
-    std::vector<rfn::Slot> hs(ns);
-    HIP_OK(hipMemcpy(hs.data(), (const rfn::Slot*)r.d_slots + ((size_t)pass * V + v) * ns, sizeof(rfn::Slot) * ns,
-                     hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < ns; k++) {
-      if (codes) codes[k] = hs[k].code;
-      if (Sw) Sw[k] = hs[k].Sw;
-      if (Skw) Skw[k] = hs[k].Skw;
-      if (rows) std::memcpy(rows + 7 * k, hs[k].row, sizeof(double) * 7);
-    }
-  }
-  return MANTIS_OK;
+  return slots_scatter<rfn::Slot, 7>(c, (const rfn::Slot*)r.d_slots + ((size_t)pass * V + v) * ns, ns, codes, Sw, Skw,
+                                     rows);
 }
 
 mantis_status mantis_get_smooth_pass(void* ctx, int32_t window, int32_t pass, double* e, double* J, double* prior_e,

@@ -76,6 +76,31 @@ def candidates(f):
     return [i for i in range(len(f)) if f[i] in (1, 2)]
 
 
+# The row counts at which a trip loop of the MFMA accumulations ends differently: some waves without a trip, one
+# short group, one row past whole trips, one row short of them. (A trip of the 7-column loop is 128 rows, eight
+# groups of four per wave; a trip of a calibration's wave is 32 rows of one camera, 16 with the 21-column row.)
+ROW_CLASSES = {"rows<16": lambda n: 1 <= n < 16, "16<=rows<128": lambda n: 16 <= n < 128,
+               "rows%128=1": lambda n: n > 128 and n % 128 == 1, "rows%128=127": lambda n: n > 128 and n % 128 == 127}
+# (class, cameras) of the refinement's cases: three cameras, but for the class below 128 rows, where three cameras
+# leave at most 42 candidates, all on the red and green border, whose normal matrix is singular (the plain call
+# says SINGULAR, and a weighted one is decided by its last bits); one camera's 127 candidates hold white lines.
+TAIL_CASES = [("rows<16", 3), ("16<=rows<128", 1), ("rows%128=1", 3), ("rows%128=127", 3)]
+
+
+def cut_map(landmark_map, cls, per=1, pitch=0.08):
+    """The map with landmarks dropped from the front, as test_odd_candidate_count cuts it, until `per` x its
+    candidate count is in the row class `cls`: white ones first, and on into the red and the green, which alone
+    still hold 74 candidates. Returns ((w, r, g), (X, nw, nr, ng), n_cand)."""
+    w, r, g = landmark_map
+    for drop in range(1, len(w) + len(r) + len(g)):
+        cut = (w[drop:], r[max(drop - len(w), 0):], g[max(drop - len(w) - len(r), 0):])
+        X = np.ascontiguousarray(np.concatenate(cut), np.float64).reshape(-1, 3)
+        nc = len(candidates(flags(X, pitch)))
+        if ROW_CLASSES[cls](per * nc):
+            return cut, (X, len(cut[0]), len(cut[1]), len(cut[2])), nc
+    raise AssertionError(f"no cut of the map gives {per} x n_cand in {cls}")
+
+
 def obs(T, Tbc, K, D, img, X, nw, nr, ng, f, R=12, white_thresh=12288, min_weight=24576):
     """hc_refine_obs: (codes, Sw, Skw, rows [n_cand, 7], tie [n_cand]) of one pass for one camera."""
     T = np.ascontiguousarray(T, np.float64)

@@ -250,6 +250,23 @@ def test_odd_candidate_count(mantis, lm, knocked, landmark_map):
         mantis.set_map(w, r, g)
 
 
+@pytest.mark.parametrize("cls", list(RR.ROW_CLASSES))
+def test_trip_loop_tails(mantis, lm, knocked, landmark_map, cls):
+    """The rig calibration with Tukey rows, two views of two cameras, on a map cut until a camera's n_cand rows --
+    what one wave's weighted trip loop of the three 21-column tiles runs over -- end that loop another way
+    (RR.ROW_CLASSES). The small classes leave the call STARVED, its record written."""
+    cut, landmarks, nc = RR.cut_map(landmark_map, cls)
+    try:
+        mantis.set_map(*cut)
+        spec = QR.Spec("rig", free_ext=0b10, free_int=0b11)
+        T_out, res, st = _check_call(mantis, spec, lm, [fr[:2] for fr in knocked["frames"][:2]], knocked["ext"][:2],
+                                     knocked["kd"][:2], knocked["T0"][:2], "tukey", landmarks=landmarks)
+        assert res.n_cand == nc and RR.ROW_CLASSES[cls](res.n_cand)
+        print(cls, nc, res.status, res.iterations_run, list(res.n_obs)[:5])
+    finally:
+        mantis.set_map(*landmark_map)
+
+
 def test_small_pitched_frame(mantis, lm):
     """322 x 242 (neither a multiple of 4) with step_bytes = 1000 > 3 W: staged through the pitch conversion."""
     w, h = 322, 242

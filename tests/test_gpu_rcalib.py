@@ -259,6 +259,22 @@ def test_odd_candidate_count(mantis, lm, scene, landmark_map):
         mantis.set_map(w, r, g)
 
 
+@pytest.mark.parametrize("cls", list(RR.ROW_CLASSES))
+def test_trip_loop_tails(mantis, lm, scene, landmark_map, cls):
+    """Two views of two cameras on a map cut until a camera's n_cand rows -- what one wave's trip loop of the
+    three 21-column tiles runs over -- end that loop another way (RR.ROW_CLASSES). The small classes leave the
+    call STARVED, its record written."""
+    cut, landmarks, nc = RR.cut_map(landmark_map, cls)
+    try:
+        mantis.set_map(*cut)
+        T_out, res = _check_call(mantis, lm, [fr[1:3] for fr in scene["frames"][:2]], scene["ext"][1:3],
+                                 scene["T0"][:2], 0b10, 0b11, landmarks=landmarks)
+        assert res.n_cand == nc and RR.ROW_CLASSES[cls](res.n_cand)
+        print(cls, nc, res.status, res.iterations_run, list(res.n_obs)[:5])
+    finally:
+        mantis.set_map(*landmark_map)
+
+
 def test_small_pitched_frame(mantis, lm):
     """322 x 242 (neither a multiple of 4) with step_bytes = 1000 > 3 W: staged through the pitch conversion."""
     import mantis_amd as M

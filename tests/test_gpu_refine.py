@@ -151,6 +151,22 @@ def test_odd_candidate_count(mantis, lm, rigs4, landmark_map):
     assert np.array_equal(mantis.line_flags(0.08), RR.flags(lm[0], 0.08))
 
 
+@pytest.mark.parametrize("cls,Cn", RR.TAIL_CASES)
+def test_trip_loop_tails(mantis, lm, rigs4, landmark_map, cls, Cn):
+    """Cn cameras on a map cut until the rig's Cn n_cand rows end the accumulation's trip loop another way
+    (RR.ROW_CLASSES, RR.TAIL_CASES; the full map's rigs have 540 rows per camera, so every wave has whole trips
+    there). The few rows of the smallest class leave the pass STARVED: its record is written all the same."""
+    cut, landmarks, nc = RR.cut_map(landmark_map, cls, per=Cn)
+    try:
+        mantis.set_map(*cut)
+        res = _check_call(mantis, lm, rigs4["frames"][0][:Cn], rigs4["ext"][:Cn], RR.shift(rigs4["Twb"][0]),
+                          landmarks=landmarks)
+        assert res.n_cand == nc and RR.ROW_CLASSES[cls](Cn * res.n_cand)
+        print(cls, nc, res.status, res.iterations_run, list(res.n_obs)[:5])
+    finally:
+        mantis.set_map(*landmark_map)
+
+
 def test_line_flags_on_the_context(mantis, lm):
     X = lm[0]
     for pitch in (0.08, 0.32, 0.05, 0.08):

@@ -177,6 +177,24 @@ def test_odd_candidate_count(mantis, lm, rigs4, landmark_map, loss):
         mantis.set_map(w, r, g)
 
 
+@pytest.mark.parametrize("loss", LOSSES)
+@pytest.mark.parametrize("cls,Cn", RR.TAIL_CASES)
+def test_trip_loop_tails(mantis, lm, rigs4, landmark_map, cls, Cn, loss):
+    """Cn cameras on a map cut until the rig's Cn n_cand rows end the weighted accumulation's trip loop another
+    way (RR.ROW_CLASSES, RR.TAIL_CASES), all inside one 2048-row chunk; the eight-camera rig of test_record_parity
+    is the case that crosses the chunk and the kept keys. The smallest class leaves the pass STARVED, its record
+    written."""
+    cut, landmarks, nc = RR.cut_map(landmark_map, cls, per=Cn)
+    try:
+        mantis.set_map(*cut)
+        res, st = _check_call(mantis, lm, rigs4["frames"][0][:Cn], rigs4["ext"][:Cn], RR.shift(rigs4["Twb"][0]), loss,
+                              landmarks=landmarks)
+        assert res.n_cand == nc and RR.ROW_CLASSES[cls](Cn * res.n_cand)
+        print(cls, loss, nc, res.status, res.iterations_run, list(res.n_obs)[:5])
+    finally:
+        mantis.set_map(*landmark_map)
+
+
 def _pair_maps(lm, rigs4, T0):
     """Two-landmark maps of neighbours on one white line, seen by camera 0 at T0: one whose two candidates both
     give a row, one where only the first does (the host's codes on the full map: an observation does not depend

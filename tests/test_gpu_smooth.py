@@ -275,6 +275,26 @@ def test_odd_candidate_count(small, lm, small5, landmark_map):
         small.set_map(w, r, g)
 
 
+@pytest.mark.parametrize("cls", list(RR.ROW_CLASSES))
+def test_trip_loop_tails(small, lm, small5, landmark_map, cls):
+    """One view of one camera on a map cut until its n_cand rows end the accumulation's trip loop another way
+    (RR.ROW_CLASSES); the small classes leave the window STARVED, its record written. k_smooth_acc and
+    k_refine_step run one accumulation: pass 0's acc28 of the refinement from the same frame and pose has the
+    same bytes."""
+    cut, landmarks, nc = RR.cut_map(landmark_map, cls)
+    fr, ext, T0 = [small5["frames"][0][:1]], small5["ext"][:1], SR.starts(small5)[:1]
+    try:
+        small.set_map(*cut)
+        res, _ = _check_call(small, lm, fr, ext, T0, None, landmarks=landmarks)
+        assert res.n_cand == nc and RR.ROW_CLASSES[cls](res.n_cand)
+        print(cls, nc, res.status, res.iterations_run, list(res.n_obs)[:5])
+        acc = small.smooth_record(0, 0, 0)[5]
+        small.refine_batch(_images(fr, ext), 1, T0[0], record=1)
+        assert small.refine_record(0, 0)[5].tobytes() == acc.tobytes()
+    finally:
+        small.set_map(*landmark_map)
+
+
 @pytest.mark.parametrize("iterations", [0, 10])
 def test_iteration_counts(small, lm, small5, iterations):
     fr, T0, mo = _chain(small5, [0, 1, 2])
