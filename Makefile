@@ -15,7 +15,7 @@ CSRC = mantis_amd/csrc
 all: product tools oracle
 
 product: mantis_amd/libmantis_amd.so
-mantis_amd/libmantis_amd.so: $(CSRC)/api.hip $(CSRC)/kernels.hip $(CSRC)/gn_impl.hip $(CSRC)/dense_impl.hip $(wildcard $(CSRC)/*.h) $(CSRC)/mk_rpp_np.inc $(CSRC)/markov_impl.hip $(CSRC)/track_impl.hip $(CSRC)/mk_track.h $(CSRC)/mcl_impl.hip $(CSRC)/mk_mcl.h $(CSRC)/mcl_modes_impl.hip $(CSRC)/mk_mcl_modes.h $(CSRC)/mcl_color_impl.hip $(CSRC)/mk_mcl_color.h $(CSRC)/refine_impl.hip $(CSRC)/refine_robust_impl.hip $(CSRC)/mk_refine.h $(CSRC)/smooth_impl.hip $(CSRC)/mk_smooth.h $(CSRC)/linecal_impl.hip $(CSRC)/mk_linecal.h $(CSRC)/mk_calib.h $(CSRC)/mk_icalib.h $(CSRC)/mcl_refine_impl.hip $(CSRC)/mk_mcl_refine.h include/mantis.h include/mantis_ros.h
+mantis_amd/libmantis_amd.so: $(CSRC)/api.hip $(CSRC)/kernels.hip $(CSRC)/gn_impl.hip $(CSRC)/dense_impl.hip $(wildcard $(CSRC)/*.h) $(CSRC)/mk_rpp_np.inc $(CSRC)/markov_impl.hip $(CSRC)/track_impl.hip $(CSRC)/mk_track.h $(CSRC)/mcl_impl.hip $(CSRC)/mk_mcl.h $(CSRC)/mcl_modes_impl.hip $(CSRC)/mk_mcl_modes.h $(CSRC)/mcl_color_impl.hip $(CSRC)/mk_mcl_color.h $(CSRC)/refine_impl.hip $(CSRC)/refine_robust_impl.hip $(CSRC)/mk_refine.h $(CSRC)/smooth_impl.hip $(CSRC)/mk_smooth.h $(CSRC)/linecal_impl.hip $(CSRC)/mk_linecal.h $(CSRC)/mk_calib.h $(CSRC)/mk_icalib.h $(CSRC)/mcl_refine_impl.hip $(CSRC)/mk_mcl_refine.h $(CSRC)/hostbuf.h include/mantis.h include/mantis_ros.h
 	$(HIPCC) $(HIPFLAGS) -shared -pthread -o $@ $(CSRC)/api.hip -lrccl
 
 tools: build/libmantis_hostcheck.so tools/libmantis_synth.so

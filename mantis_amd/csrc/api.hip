@@ -30,7 +30,17 @@
 
 #include <rccl/rccl.h>
 
+#include "hostbuf.h"
 #include "kernels.hip"
+
+namespace mk {  // element types of Ctx's buffers that the *_impl.hip files define
+struct TrackState;
+struct DenseJob;
+struct RefineRig;
+struct LinecalState;
+namespace refine { struct Slot; }
+namespace linecal { struct RobustCell; }
+}  // namespace mk
 
 using namespace mk;
 
@@ -108,8 +118,32 @@ inline float rng_gauss(uint64_t& state) {
     }                                                                             \
   } while (0)
 
-struct Ctx {
-  mantis_config cfg{};
+// the two kinds of memory a context owns (hostbuf.h)
+struct DevAlloc {
+  static constexpr const char* kFailed = "hipMalloc failed";
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
+  }
+  static void free(void* p) { (void)hipFree(p); }
+};
+struct PinAlloc {
+  static constexpr const char* kFailed = "hipHostMalloc failed";
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+  }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T>
+using DevBuf = Buf<T, DevAlloc>;
+template <class T>
+using PinBuf = Buf<T, PinAlloc>;
+
+// A context's streams and events. A base of Ctx, so that they are destroyed after
+// Ctx's own members, its memory, are freed: events first, then the streams
+// (mantis_destroy's order).
+struct CtxStreams {
   hipStream_t s = nullptr;
   hipStream_t s_copy = nullptr;     // side stream: the gaussian stream's H2D, overlapped with RPP
   hipEvent_t ev_gauss = nullptr;    // ... which s waits on before scoring
@@ -118,11 +152,26 @@ struct Ctx {
   // context was most of a step's host CPU time); calls of at most
   // spin_frames frames spin (latency).
   hipEvent_t ev_wait = nullptr;
+  std::vector<hipEvent_t> ev;  // profiling
+  CtxStreams() = default;
+  CtxStreams(const CtxStreams&) = delete;
+  CtxStreams& operator=(const CtxStreams&) = delete;
+  ~CtxStreams() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    if (ev_gauss) (void)hipEventDestroy(ev_gauss);
+    if (ev_wait) (void)hipEventDestroy(ev_wait);
+    if (s_copy) (void)hipStreamDestroy(s_copy);
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+struct Ctx : CtxStreams {
+  mantis_config cfg{};
   int spin_frames = 16;
   std::string err;
   uint64_t rng_state = 1;
   // map
-  double* d_lm = nullptr;
+  DevBuf<double> d_lm;
   int nw = 0, nr = 0, ng = 0;
   // capacity
   int F = 0, Wmax = 0, Hmax = 0;
@@ -135,14 +184,13 @@ struct Ctx {
   size_t plane = 0;
   int pool_cap = 0;
   // device workspace
-  uint16_t* d_lroot = nullptr;  // hysteresis run extents (k_hyst_*), then contour run starts
+  DevBuf<uint16_t> d_lroot;  // hysteresis run extents (k_hyst_*), then contour run starts
   size_t lstride = 0;            // d_lroot entries per frame: max(plane, tiles x FTW x FTH)
   size_t fstride = 0;            // d_strong bytes per frame: plane rounded up to a dword (32-bit flag atomics)
-  uint8_t *d_bgr = nullptr, *d_strong = nullptr, *d_edge = nullptr,
-          *d_det = nullptr, *d_mask = nullptr;
-  int32_t* d_lab = nullptr;
-  uint32_t *d_eb = nullptr, *d_b1 = nullptr, *d_b2 = nullptr;  // bit planes
-  uint32_t* d_mbits = nullptr;  // cleanImageByEdge mask bits (k_morph -> k_frame_score)
+  DevBuf<uint8_t> d_bgr, d_strong, d_edge, d_det, d_mask;
+  DevBuf<int32_t> d_lab;
+  DevBuf<uint32_t> d_eb, d_b1, d_b2;  // bit planes
+  DevBuf<uint32_t> d_mbits;  // cleanImageByEdge mask bits (k_morph -> k_frame_score)
   size_t bstride = 0;                                           // words per frame
   int morph_bh = 48;       // k_morph output rows per band (MB_BH, or MB_BH_NARROW at wide max_width)
   int morph_walk = 1 << 20;  // k_morph_walk rows per segment (0: the LDS band kernel k_morph); MANTIS_MORPH_WALK
@@ -154,27 +202,27 @@ struct Ctx {
   size_t hyst_rec_lds = 0;  // dynamic LDS k_hyst_rec may take (a frame's candidate words)
   bool pf_split = true;    // small batches: each particle-filter iteration over several blocks per frame
                            // (k_score_pf_part); MANTIS_PF_SPLIT=0 keeps one block per frame
-  uint32_t* d_dbits = nullptr;                                  // padded detector bits
-  uint32_t* d_tbits = nullptr;                                  // the same in 32x32 tiles (k_trace_borders)
+  DevBuf<uint32_t> d_dbits;                                     // padded detector bits
+  DevBuf<uint32_t> d_tbits;                                     // the same in 32x32 tiles (k_trace_borders)
   size_t tstride = 0;
-  int32_t* d_rowb = nullptr;  // run CCL row bases, rstride per frame
+  DevBuf<int32_t> d_rowb;  // run CCL row bases, rstride per frame
   size_t rstride = 0;
   size_t dstride = 0;
-  FrameDesc* d_frames = nullptr;
-  Border* d_borders = nullptr;
-  int32_t *d_bcount = nullptr, *d_boff = nullptr, *d_pool = nullptr, *d_scratch = nullptr;
-  QuadRec* d_quads = nullptr;
-  RppOut* d_rpp = nullptr;
-  RppItem* d_items = nullptr;
-  rpp::Refine* d_refine = nullptr;
-  int32_t *d_jobs0 = nullptr, *d_jobs1 = nullptr;  // RPP ObjPose job queues
-  RppQueue* d_rq = nullptr;
+  DevBuf<FrameDesc> d_frames;
+  DevBuf<Border> d_borders;
+  DevBuf<int32_t> d_bcount, d_boff, d_pool, d_scratch;
+  DevBuf<QuadRec> d_quads;
+  DevBuf<RppOut> d_rpp;
+  DevBuf<RppItem> d_items;
+  DevBuf<rpp::Refine> d_refine;
+  DevBuf<int32_t> d_jobs0, d_jobs1;  // RPP ObjPose job queues
+  DevBuf<RppQueue> d_rq;
   int rpp_blocks = 0;
   // ObjPose tail compaction (k_objpose_q rounds): two spill pools of op_cap
   // lanes (kOpFields doubles + a job id each), their counters, rounds per queue
-  double* d_opool[2] = {nullptr, nullptr};
-  int32_t* d_ojob[2] = {nullptr, nullptr};
-  int32_t* d_octl = nullptr;  // [queue][round]: entries, next (zeroed once per RPP launch sequence)
+  DevBuf<double> d_opool[2];
+  DevBuf<int32_t> d_ojob[2];
+  DevBuf<int32_t> d_octl;  // [queue][round]: entries, next (zeroed once per RPP launch sequence)
   int32_t op_cap = 0;
   int op_rounds = 6, op_spill = 32;
   // small batches (latency): ObjPose jobs per wave and rounds (MANTIS_OP_LANES_SMALL, MANTIS_OP_ROUNDS_SMALL).
@@ -197,58 +245,56 @@ struct Ctx {
   bool counted = false;  // included in g_live_ctx
   bool vec_ok = false;
   // dense scoring (mantis_score_argmin): hypotheses, errors, counts; (err, idx) pairs per rank
-  double *d_dense_c2w = nullptr, *d_dense_err = nullptr, *d_pairs = nullptr;
-  int32_t* d_dense_np = nullptr;
-  size_t dense_cap = 0;
-  void* d_dense_jobs = nullptr;  // mantis_score_argmin_batch: per-frame DenseJob records
-  size_t dense_pairs_cap = 0;    // doubles d_pairs holds (0: the 64-rank single-frame buffer)
-  size_t dense_jobs_cap = 0;     // DenseJob records d_dense_jobs holds
+  DevBuf<double> d_dense_c2w, d_dense_err, d_pairs;  // d_pairs: at least the 64-rank single-frame buffer
+  DevBuf<int32_t> d_dense_np;
+  size_t dense_cap = 0;              // hypotheses d_dense_c2w (x 12) / _err / _np hold
+  DevBuf<DenseJob> d_dense_jobs;  // mantis_score_argmin_batch: per-frame records
   // rig GN (cfg.gn_enable): per-camera inv(T_base_cam), per-rig poses, correspondences
-  GnCam* d_gncam = nullptr;
-  RigGnIO* d_rigio = nullptr;
-  double* d_gnobs = nullptr;
-  double* d_gnacc = nullptr;  // per-rig accumulator slots (kGnSlot doubles), all-reduced across camera shards
+  DevBuf<GnCam> d_gncam;
+  DevBuf<RigGnIO> d_rigio;
+  DevBuf<double> d_gnobs;
+  DevBuf<double> d_gnacc;  // per-rig accumulator slots (kGnSlot doubles), all-reduced across camera shards
   int gn_rigs = 0, gn_cpr = 0;
   int gn_last_rigs = 0, gn_last_local = 0;  // shape of the last rig GN run (mantis_get_rig_gn)
-  HypRec *d_gen = nullptr, *d_hyps = nullptr;
-  FrameState* d_st = nullptr;
-  ScoreState* d_sst = nullptr;  // scoring state between k_score_init / _pf / _final
-  FrameDebug* d_dbg = nullptr;
-  mantis_cam_result* d_res = nullptr;
-  float* d_gauss = nullptr;
-  int32_t* d_gtotal = nullptr;
+  DevBuf<HypRec> d_gen, d_hyps;
+  DevBuf<FrameState> d_st;
+  DevBuf<ScoreState> d_sst;  // scoring state between k_score_init / _pf / _final
+  DevBuf<FrameDebug> d_dbg;
+  DevBuf<mantis_cam_result> d_res;
+  DevBuf<float> d_gauss;
+  DevBuf<int32_t> d_gtotal;
   // pinned host
-  float* h_gauss = nullptr;
-  uint64_t* h_states = nullptr;
+  PinBuf<float> h_gauss;
+  PinBuf<uint64_t> h_states;
   std::vector<uint64_t> frame_rng;  // cv::RNG state after each frame of the last process call (FrameDebug); empty after a failed one
-  mantis_cam_result* h_res = nullptr;
-  FrameState* h_st = nullptr;
-  int32_t* h_gtotal = nullptr;
-  FrameDesc* h_frames = nullptr;
+  PinBuf<mantis_cam_result> h_res;
+  PinBuf<FrameState> h_st;
+  PinBuf<int32_t> h_gtotal;
+  PinBuf<FrameDesc> h_frames;
   // profiling
   bool prof = false;
   std::vector<std::string> ev_names;
-  std::vector<hipEvent_t> ev;
   std::vector<float> last_ms;
   std::vector<std::string> last_names;
   std::vector<void*> user_allocs;
   // multi-GPU
   void* comm = nullptr;  // ncclComm_t
   int nranks = 1, rank = 0;
-  double* d_gn28 = nullptr;
+  DevBuf<double> d_gn28;
   // camera-sharded rigs (mantis_process_rig_sharded): local frames' global
   // indices, gathered (global index, PF flag) pairs, global PF flags, result records
-  int32_t *d_sh_gidx = nullptr, *d_sh_pf = nullptr, *d_sh_flags = nullptr;
-  int32_t* h_sh_flags = nullptr;
+  DevBuf<int32_t> d_sh_gidx, d_sh_pf, d_sh_flags;
+  PinBuf<int32_t> h_sh_flags;
   size_t sh_cap = 0;  // global frames the shard buffers hold
-  uint8_t *d_sh_rec = nullptr, *h_sh_rec = nullptr;
+  DevBuf<uint8_t> d_sh_rec;
+  PinBuf<uint8_t> h_sh_rec;
   size_t sh_rec_bytes = 0;
   int gauss_cap = 0;  // frames of gaussians h_gauss / d_gauss / h_states hold
   // legacy rig weighting (cfg.rig_weighting): jobs, (sum, count) per job, the
   // last batch's record per rig (mantis_get_rig_weights)
-  RigWJob* d_rwjobs = nullptr;
-  double* d_rwout = nullptr;
-  size_t rw_cap = 0;
+  DevBuf<RigWJob> d_rwjobs;
+  DevBuf<double> d_rwout;
+  size_t rw_cap = 0;  // jobs d_rwjobs holds; d_rwout twice as many doubles
   int rw_rigs = 0, rw_C = 0;
   std::vector<double> rw_weights, rw_c2w, rw_sums;
   std::vector<int32_t> rw_chosen;
@@ -256,10 +302,10 @@ struct Ctx {
   bool has_prior = false;
   double prior_Twb[16];
   // Markov yaw filters (markov_impl.hip): markov_n planes of 360 bins, per-filter operations
-  double* d_markov = nullptr;
-  MarkovOp* d_mops = nullptr;
+  DevBuf<double> d_markov;
+  DevBuf<MarkovOp> d_mops;
   int markov_n = 0;
-  int32_t* d_agree = nullptr;  // sharded calls: the failure flag all-reduced by agree()
+  DevBuf<int32_t> d_agree;  // sharded calls: the failure flag all-reduced by agree()
   bool agreed_fail = false;     // the last failure was agreed on by every rank (agree())
   // hipGraphs of the rig-latency path (batches of at most fc_small_frames
   // frames): the call's device work as two graphs -- image stages .. RPP ..
@@ -282,17 +328,15 @@ struct Ctx {
   // rig tracking (track_impl.hip): workspaces allocated on first use and grown
   // to the largest call, and the last call's shape (mantis_get_track_record)
   struct Track {
-    void* d_in = nullptr;   // predictions, extrinsics, gaussians (one H2D copy from h_in)
-    void* h_in = nullptr;   // pinned
-    size_t in_cap = 0;
-    void* d_state = nullptr;  // per rig: current pose and error between the launches
-    void* d_res = nullptr;    // per rig: mantis_track_result
-    void* h_res = nullptr;    // pinned
-    int rig_cap = 0;
-    void *d_Twb = nullptr, *d_c2w = nullptr, *d_pf = nullptr;  // per pass x rig x particle (x camera)
-    long long* d_sums = nullptr;
-    int32_t* d_cnt = nullptr;
-    size_t pose_cap = 0, task_cap = 0;  // entries of d_Twb; of d_c2w / d_pf / d_sums / d_cnt
+    DevBuf<uint8_t> d_in;  // predictions, extrinsics, gaussians (one H2D copy from h_in)
+    PinBuf<uint8_t> h_in;
+    DevBuf<TrackState> d_state;  // per rig: current pose and error between the launches
+    DevBuf<mantis_track_result> d_res;  // per rig
+    PinBuf<mantis_track_result> h_res;
+    DevBuf<Xf> d_Twb, d_c2w;  // per pass x rig x particle (x camera)
+    DevBuf<PoseF> d_pf;
+    DevBuf<long long> d_sums;
+    DevBuf<int32_t> d_cnt;
     int rigs = 0, C = 0, P = 0, I = 0, record = 0;  // the last call
   } trk;
   // Monte Carlo localization (mcl_impl.hip): the particle set lives here
@@ -302,32 +346,37 @@ struct Ctx {
     bool live = false;          // an init has run (mantis_mcl_reset clears)
     mantis_mcl_params p{};
     int N = 0, cap = 0, cur = 0;  // particles, capacity, which of d_T holds the set
-    void* d_T[2] = {nullptr, nullptr};  // Xf x cap: the set and the resampling target
-    double *d_L = nullptr, *d_Lprev = nullptr;  // log-weights; those before the last step
-    unsigned long long *d_q = nullptr, *d_cum = nullptr;
-    int32_t* d_anc = nullptr;
-    void *d_in = nullptr, *h_in = nullptr;  // extrinsics, motion, gaussians (one H2D copy); pinned
-    void *d_c2w = nullptr, *d_pf = nullptr;  // cap x 8
-    long long* d_sums = nullptr;
-    int32_t* d_cnt = nullptr;
-    void *d_res = nullptr, *h_res = nullptr;  // the step's result record; pinned
+    DevBuf<Xf> d_T[2];  // cap: the set and the resampling target
+    DevBuf<double> d_L, d_Lprev;  // log-weights; those before the last step
+    DevBuf<unsigned long long> d_q, d_cum;
+    DevBuf<int32_t> d_anc;
+    DevBuf<uint8_t> d_in;  // extrinsics, motion, gaussians (one H2D copy)
+    PinBuf<uint8_t> h_in;
+    DevBuf<Xf> d_c2w;  // cap x 8
+    DevBuf<PoseF> d_pf;
+    DevBuf<long long> d_sums;
+    DevBuf<int32_t> d_cnt;
+    DevBuf<mantis_mcl_result> d_res;  // the step's result record
+    PinBuf<mantis_mcl_result> h_res;
     bool has_record = false;  // a step has run since the init
     int rec_C = 0, rec_pred = 0;  // its cameras; which of d_T holds its predicted poses
     // the modes of the last step (mcl_modes_impl.hip): the record and, behind it, select_mode's kept count; pinned
-    void *d_modes = nullptr, *h_modes = nullptr;
+    DevBuf<uint8_t> d_modes;
+    PinBuf<uint8_t> h_modes;
     bool has_modes = false;  // mantis_mcl_modes has run since the last step
     struct mantis_mcl_modes modes;  // its answer: what mantis_mcl_select_mode commits to
     double modes_g = 0;             // the grid spacing its keys were taken with
     // the modes refined (mcl_refine_impl.hip): mantis_mcl_refine_modes(apply = 1) has moved particles since
     // the last step; the 8 per-mode counters of k_mcl_recentre and their pinned copy
     bool recentred = false;
-    int32_t *d_moved = nullptr, *h_moved = nullptr;
+    DevBuf<int32_t> d_moved;
+    PinBuf<int32_t> h_moved;
     // the colour evidence (mcl_color_impl.hip): what mantis_mcl_set_color left (enable 0 until then), the
     // (csum, cn) of the last step with colour on, N x C, its pooled Ec and charge, N
     mantis_mcl_color_params color{};
-    long long* d_csums = nullptr;
-    int32_t* d_ccnt = nullptr;
-    double *d_Ec = nullptr, *d_charge = nullptr;
+    DevBuf<long long> d_csums;
+    DevBuf<int32_t> d_ccnt;
+    DevBuf<double> d_Ec, d_charge;
     int color_cap = 0;                      // particles the colour buffers hold
     int rec_color = 0, rec_color_min = 0;   // the last step's enable and min_color_projections
   } mcl;
@@ -339,24 +388,23 @@ struct Ctx {
     std::vector<uint8_t> flags;
     double pitch = 0;  // of `flags`; 0 = none cached
     int n_cand = 0;
-    int32_t* d_cand = nullptr;  // n_cand: landmark | axis << 16
-    int cand_cap = 0;
-    void *d_gncam = nullptr, *d_state = nullptr, *h_state = nullptr;  // per camera; per rig (h: pinned)
-    double *d_recT = nullptr, *d_recAcc = nullptr;                   // [pass][rig][16] / [28]
+    DevBuf<int32_t> d_cand;  // n_cand: landmark | axis << 16
+    DevBuf<GnCam> d_gncam;   // per camera
+    DevBuf<RefineRig> d_state;  // per rig
+    PinBuf<uint8_t> h_state;    // both
+    DevBuf<double> d_recT, d_recAcc;  // [pass][rig][16] / [28]
     int rig_cap = 0, cam_cap = 0;
-    void* d_slots = nullptr;  // [pass (record) or one][rig][C n_cand]
-    size_t slot_cap = 0;
+    DevBuf<refine::Slot> d_slots;  // [pass (record) or one][rig][C n_cand]
     int rigs = 0, C = 0, I = 0, record = 0, cands = 0;  // the last call
     std::vector<int32_t> runs;                          // its rigs' iterations_run
     // the robust rows (refine_robust_impl.hip): what mantis_refine_set_robust left (loss 0 until
     // then), the rigs' stats (d: per call, h: pinned, of the last call) and, for a record, every
     // pass's keys and weights laid out as d_slots
     mantis_refine_robust_params robust{};
-    mantis_refine_robust_stats *d_rstats = nullptr, *h_rstats = nullptr;
-    int rstat_cap = 0;
-    uint32_t* d_rkeys = nullptr;
-    double* d_rweights = nullptr;
-    size_t rslot_cap = 0;
+    DevBuf<mantis_refine_robust_stats> d_rstats;
+    PinBuf<mantis_refine_robust_stats> h_rstats;
+    DevBuf<uint32_t> d_rkeys;
+    DevBuf<double> d_rweights;
     int rec_loss = 0;  // the last call's loss
   } rf;
   // the three calibrations (linecal_impl.hip): workspaces grown to the largest call of their
@@ -365,24 +413,24 @@ struct Ctx {
   // kind leaves the last record of the others readable. lds_ok: k_linecal_solve may take its
   // dynamic LDS (asked once, by the rig calibration only)
   struct Linecal {
-    void *d_state = nullptr, *h_state = nullptr;  // LinecalState; h: pinned, with the poses, accumulators and counts behind it
-    double *d_T = nullptr, *d_acc = nullptr, *d_Y = nullptr, *d_Wt = nullptr;
-    int32_t *d_cnt = nullptr, *d_pd = nullptr;
+    DevBuf<LinecalState> d_state;
+    PinBuf<uint8_t> h_state;  // the LinecalState with the poses, accumulators and counts behind it
+    DevBuf<double> d_T, d_acc, d_Y, d_Wt;
+    DevBuf<int32_t> d_cnt, d_pd;
     // [pass][view][16], [pass][C][16] (with J_ext), [pass][C][8] (with J_int), [pass][view][C][kAcc]
-    double *d_recT = nullptr, *d_recE = nullptr, *d_recKD = nullptr, *d_recAcc = nullptr;
-    void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
+    DevBuf<double> d_recT, d_recE, d_recKD, d_recAcc;
+    DevBuf<uint8_t> d_slots;  // [pass (record) or one][view][C n_cand] of the kind's Slot
     int view_cap = 0;
-    size_t slot_cap = 0, racc_cap = 0;
     bool lds_asked[2] = {false, false}, lds_ok[2] = {false, false};  // [robust rows off, on]: two instantiations
     int rigs = 0, C = 0, record = 0, cands = 0, runs = 0;  // the last call
     // the robust rows (mantis_calib_set_robust): every slot's key, laid out as d_slots; the
     // weights, only as a record; the selection tables of every pass; the (view, camera) cells of
     // a pass; the stats (d: of the call, h: pinned, of the last call) and the last call's loss
-    uint32_t *d_rkeys = nullptr, *d_rtab = nullptr;
-    double* d_rweights = nullptr;
-    void* d_rcells = nullptr;
-    mantis_calib_robust_stats *d_rstats = nullptr, *h_rstats = nullptr;
-    size_t rkey_cap = 0, rweight_cap = 0;
+    DevBuf<uint32_t> d_rkeys, d_rtab;
+    DevBuf<double> d_rweights;
+    DevBuf<linecal::RobustCell> d_rcells;
+    DevBuf<mantis_calib_robust_stats> d_rstats;
+    PinBuf<uint8_t> h_rstats;  // the stats with the cells behind them
     int rcell_cap = 0, rec_loss = 0;
   } cb, ib, rb;  // extrinsic, intrinsic, rig
   // what mantis_calib_set_robust left for the three of them (loss 0 until then)
@@ -392,10 +440,10 @@ struct Ctx {
   // states, the windows' results and the final blocks (one copy back); in: the motions' Transforms,
   // the priors and the cameras' inverse extrinsics; work: the chain's blocks and the pass records
   struct Smooth {
-    uint8_t *d_out = nullptr, *h_out = nullptr, *d_in = nullptr, *h_in = nullptr;  // h: pinned
-    double* d_work = nullptr;
-    void* d_slots = nullptr;  // [pass (record) or one][view][C n_cand]
-    size_t out_cap = 0, in_cap = 0, work_cap = 0, slot_cap = 0;
+    DevBuf<uint8_t> d_out, d_in;
+    PinBuf<uint8_t> h_out, h_in;
+    DevBuf<double> d_work;
+    DevBuf<refine::Slot> d_slots;  // [pass (record) or one][view][C n_cand]
     int windows = 0, N = 0, C = 0, P = 0, record = 0, cands = 0, lay_F = 0;  // the last call
     std::vector<int32_t> runs;  // its windows' iterations_run
   } sm;
@@ -494,9 +542,6 @@ ScreenCam screen_cam_cached(Ctx* c, const Cam& cm) {
   return sc;
 }
 
-template <class T>
-mantis_status dalloc(Ctx* c, T** p, size_t count);
-
 // Stage the frames into the batch: device-resident contiguous inputs are
 // used in place; everything else is copied (pitch-converted) into d_bgr.
 mantis_status stage_frames(Ctx* c, const mantis_image* cams, int n, int& W, int& H) {
@@ -520,8 +565,7 @@ mantis_status stage_frames(Ctx* c, const mantis_image* cams, int n, int& W, int&
       if (!c->d_bgr) {
         // the staging buffer only exists once a host (or pitched) frame arrives:
         // device-resident callers keep its max_cams x 3 W H bytes of HBM
-        if (dalloc(c, &c->d_bgr, (size_t)c->F * c->Wmax * c->Hmax * 3) != MANTIS_OK) {
-          c->d_bgr = nullptr;
+        if (c->d_bgr.alloc(c, (size_t)c->F * c->Wmax * c->Hmax * 3) != MANTIS_OK) {
           c->err = "hipMalloc of the frame staging buffer failed";
           return MANTIS_ERR_OOM;
         }
@@ -642,7 +686,7 @@ mantis_status run_hyst_ccl(Ctx* c, int n, int W, int H, bool edge_bytes) {
   // mark values 4..255 (the denser bands' flags are <= 3); the flag plane is cleared when they wrap
   c->hyst_epoch = c->hyst_epoch >= 255 ? 4 : c->hyst_epoch + 1;
   if (c->hyst_epoch == 4) HIP_OK(hipMemsetAsync(c->d_strong, 0, c->fstride * (size_t)c->F, c->s));
-  HystRuns hr{(uint32_t*)c->d_lroot, c->d_lab, c->d_strong, c->d_rowb, c->lstride / 2, P, c->fstride, c->rstride, P / 2,
+  HystRuns hr{(uint32_t*)c->d_lroot.get(), c->d_lab, c->d_strong, c->d_rowb, c->lstride / 2, P, c->fstride, c->rstride, P / 2,
               HB_ROWS * ((W + 1) / 2), c->d_st, c->hyst_epoch};
   // list counters |A|, |B| of every frame (rowb[H + 1], rowb[H + 2])
   HIP_OK(hipMemset2DAsync(c->d_rowb + H + 1, c->rstride * sizeof(int32_t), 0, 2 * sizeof(int32_t), n, c->s));
@@ -884,11 +928,11 @@ mantis_status run_score(Ctx* c, int n, int n_gauss, bool copy_gauss = true) {
   } else if (ml)
     k_score_pf<kPfThreads, kPfSplit, true><<<n, kPfThreads, ml, c->s>>>(
         c->d_frames, c->d_mbits, c->bstride, L, c->d_st, c->d_gauss, c->d_res, c->d_dbg, c->d_sst, c->cfg.particles,
-        c->cfg.iterations, c->cfg.grid_spacing, 9, pf_init, c->d_hyps, (unsigned char*)c->d_gen);
+        c->cfg.iterations, c->cfg.grid_spacing, 9, pf_init, c->d_hyps, (unsigned char*)c->d_gen.get());
   else
     k_score_pf<kPfThreads, kPfSplit, false><<<n, kPfThreads, 0, c->s>>>(
         c->d_frames, c->d_mbits, c->bstride, L, c->d_st, c->d_gauss, c->d_res, c->d_dbg, c->d_sst, c->cfg.particles,
-        c->cfg.iterations, c->cfg.grid_spacing, 9, pf_init, c->d_hyps, (unsigned char*)c->d_gen);
+        c->cfg.iterations, c->cfg.grid_spacing, 9, pf_init, c->d_hyps, (unsigned char*)c->d_gen.get());
   mark(c, "score_pf_yaw/k_score_pf");
   // small batches: the 81 shifts over several blocks per frame (large ones
   // scored them at the end of k_score_pf)
@@ -934,25 +978,14 @@ using mk::shard::mat4_inv_rigid;
 using mk::shard::mat4_mul;
 using mk::shard::quat_to_mat4;
 
-template <class T>
-mantis_status dalloc(Ctx* c, T** p, size_t count);
-template <class T>
-mantis_status halloc(Ctx* c, T** p, size_t count);
-
 // gaussian buffers for n frames (a sharded call draws for every rig camera)
 mantis_status ensure_gauss(Ctx* c, int n) {
   if (n <= c->gauss_cap) return MANTIS_OK;
   const int per = c->cfg.particles * c->cfg.iterations * 6;
   HIP_OK(hipStreamSynchronize(c->s));
-  (void)hipFree(c->d_gauss);
-  (void)hipHostFree(c->h_gauss);
-  (void)hipHostFree(c->h_states);
-  c->d_gauss = nullptr;
-  c->h_gauss = nullptr;
-  c->h_states = nullptr;
   c->gauss_cap = 0;
-  if (dalloc(c, &c->d_gauss, (size_t)n * per) || halloc(c, &c->h_gauss, (size_t)n * per) ||
-      halloc(c, &c->h_states, (size_t)n + 1))
+  if (c->d_gauss.alloc(c, (size_t)n * per) || c->h_gauss.alloc(c, (size_t)n * per) ||
+      c->h_states.alloc(c, (size_t)n + 1))
     return MANTIS_ERR_OOM;
   c->gauss_cap = n;
   return MANTIS_OK;
@@ -1122,39 +1155,26 @@ mantis_status process_frames(Ctx* c, const mantis_image* cams, int n, const Shar
   return MANTIS_OK;
 }
 
-template <class T>
-mantis_status dalloc(Ctx* c, T** p, size_t count) {
-  if (hipMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) {
-    c->err = "hipMalloc failed";
-    return MANTIS_ERR_OOM;
-  }
-  return MANTIS_OK;
-}
-// device scratch of one C-ABI call, freed on every return path
+// device scratch of one C-ABI call: every return path waits for the stream, then frees
 struct DevScratch {
   Ctx* c;
   std::vector<void*> p;
   explicit DevScratch(Ctx* ctx) : c(ctx) {}
   template <class T>
-  bool get(T** q, size_t count) {  // true on failure (c->err set), like dalloc
-    *q = nullptr;
-    if (dalloc(c, q, count)) return true;
+  bool get(T** q, size_t count) {  // true on failure (c->err set)
+    *q = (T*)DevAlloc::alloc(sizeof(T) * std::max<size_t>(count, 1));
+    if (!*q) {
+      c->err = DevAlloc::kFailed;
+      return true;
+    }
     p.push_back((void*)*q);
     return false;
   }
   ~DevScratch() {
     if (!p.empty()) (void)hipStreamSynchronize(c->s);
-    for (void* q : p) (void)hipFree(q);
+    for (void* q : p) DevAlloc::free(q);
   }
 };
-template <class T>
-mantis_status halloc(Ctx* c, T** p, size_t count) {
-  if (hipHostMalloc((void**)p, sizeof(T) * std::max<size_t>(count, 1), hipHostMallocDefault) != hipSuccess) {
-    c->err = "hipHostMalloc failed";
-    return MANTIS_ERR_OOM;
-  }
-  return MANTIS_OK;
-}
 
 // T_base_cam of each camera, 16 doubles per camera
 std::vector<double> gather_tbc(const mantis_image* cams, int n) {
@@ -1249,9 +1269,7 @@ mantis_status mantis_create(const mantis_config* cfg_in, void** out_ctx) {
       hipEventCreateWithFlags(&c->ev_gauss, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_wait, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) {
     g_create_err = "hipSetDevice/hipStreamCreate failed";
-    if (c->s) (void)hipStreamDestroy(c->s);
-    if (c->s_copy) (void)hipStreamDestroy(c->s_copy);
-    delete c;
+    mantis_destroy(c);
     return MANTIS_ERR_DEVICE;
   }
   if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, cfg.device) != hipSuccess || c->n_cu < 1)
@@ -1328,8 +1346,7 @@ mantis_status mantis_create(const mantis_config* cfg_in, void** out_ctx) {
   if (hipFuncSetAttribute((const void*)k_hyst_band, hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)(3 * sizeof(uint32_t) * HB_ROWS * bits::words(c->Wmax))) != hipSuccess) {
     g_create_err = "max_width too large for the hysteresis band kernel";
-    (void)hipStreamDestroy(c->s);
-    delete c;
+    mantis_destroy(c);
     return MANTIS_ERR_ARG;
   }
   c->morph_bh = morph_lds(c->Wmax, MB_BH) <= 160 * 1024 ? MB_BH : MB_BH_NARROW;
@@ -1343,8 +1360,7 @@ mantis_status mantis_create(const mantis_config* cfg_in, void** out_ctx) {
                           (int)morph_lds(c->Wmax, c->morph_bh)) !=
           hipSuccess) {
     g_create_err = "max_width too large for the morphology band kernel";
-    (void)hipStreamDestroy(c->s);
-    delete c;
+    mantis_destroy(c);
     return MANTIS_ERR_ARG;
   }
   const int F = c->F;
@@ -1352,60 +1368,60 @@ mantis_status mantis_create(const mantis_config* cfg_in, void** out_ctx) {
   mantis_status st = MANTIS_OK;
   auto chk = [&](mantis_status s) { if (st == MANTIS_OK) st = s; };
   c->fstride = (c->plane + 3) & ~(size_t)3;  // the hysteresis flags take dword atomics at (root & ~3)
-  chk(dalloc(c, &c->d_strong, (size_t)F * c->fstride));
+  chk(c->d_strong.alloc(c, (size_t)F * c->fstride));
   c->lstride = (c->plane + 1) & ~(size_t)1;  // even: the hysteresis views it as u32 run extents
-  chk(dalloc(c, &c->d_lroot, (size_t)F * c->lstride));
-  chk(dalloc(c, &c->d_edge, c->plane));  // debug / single-frame byte planes (frame 0)
-  chk(dalloc(c, &c->d_det, c->plane));
-  chk(dalloc(c, &c->d_eb, (size_t)F * c->bstride));
-  chk(dalloc(c, &c->d_b1, (size_t)F * c->bstride));
-  chk(dalloc(c, &c->d_b2, (size_t)F * c->bstride));
-  chk(dalloc(c, &c->d_dbits, (size_t)F * c->dstride));
+  chk(c->d_lroot.alloc(c, (size_t)F * c->lstride));
+  chk(c->d_edge.alloc(c, c->plane));  // debug / single-frame byte planes (frame 0)
+  chk(c->d_det.alloc(c, c->plane));
+  chk(c->d_eb.alloc(c, (size_t)F * c->bstride));
+  chk(c->d_b1.alloc(c, (size_t)F * c->bstride));
+  chk(c->d_b2.alloc(c, (size_t)F * c->bstride));
+  chk(c->d_dbits.alloc(c, (size_t)F * c->dstride));
   c->tstride = tbits_words(c->Wmax + 2, c->Hmax + 2);
-  chk(dalloc(c, &c->d_tbits, (size_t)F * c->tstride));
+  chk(c->d_tbits.alloc(c, (size_t)F * c->tstride));
   c->rstride = (size_t)c->Hmax + 3 + (c->Hmax + HB_ROWS - 1) / HB_ROWS;  // + the hysteresis band run counts
-  chk(dalloc(c, &c->d_rowb, (size_t)F * c->rstride));
-  chk(dalloc(c, &c->d_mask, c->plane));
-  chk(dalloc(c, &c->d_mbits, (size_t)F * c->bstride));
-  chk(dalloc(c, &c->d_lab, (size_t)F * c->plane));
-  chk(dalloc(c, &c->d_frames, (size_t)F));
-  chk(dalloc(c, &c->d_borders, (size_t)F * kMaxBorders));
-  chk(dalloc(c, &c->d_bcount, (size_t)F * kMaxBorders));
-  chk(dalloc(c, &c->d_boff, (size_t)F * kMaxBorders));
-  chk(dalloc(c, &c->d_pool, (size_t)F * 2 * c->pool_cap));
-  chk(dalloc(c, &c->d_scratch, (size_t)F * 4 * c->pool_cap));
-  chk(dalloc(c, &c->d_quads, (size_t)F * kMaxQuads));
-  chk(dalloc(c, &c->d_rpp, (size_t)F * kMaxQuads * 2));
-  chk(dalloc(c, &c->d_items, (size_t)F * kMaxQuads * 2));
-  chk(dalloc(c, &c->d_refine, (size_t)F * kMaxQuads * 2 * rpp::kCand));
-  chk(dalloc(c, &c->d_jobs0, (size_t)F * kMaxQuads * 2));
-  chk(dalloc(c, &c->d_jobs1, (size_t)F * kMaxQuads * 2 * rpp::kCand));
-  chk(dalloc(c, &c->d_rq, 1));
+  chk(c->d_rowb.alloc(c, (size_t)F * c->rstride));
+  chk(c->d_mask.alloc(c, c->plane));
+  chk(c->d_mbits.alloc(c, (size_t)F * c->bstride));
+  chk(c->d_lab.alloc(c, (size_t)F * c->plane));
+  chk(c->d_frames.alloc(c, (size_t)F));
+  chk(c->d_borders.alloc(c, (size_t)F * kMaxBorders));
+  chk(c->d_bcount.alloc(c, (size_t)F * kMaxBorders));
+  chk(c->d_boff.alloc(c, (size_t)F * kMaxBorders));
+  chk(c->d_pool.alloc(c, (size_t)F * 2 * c->pool_cap));
+  chk(c->d_scratch.alloc(c, (size_t)F * 4 * c->pool_cap));
+  chk(c->d_quads.alloc(c, (size_t)F * kMaxQuads));
+  chk(c->d_rpp.alloc(c, (size_t)F * kMaxQuads * 2));
+  chk(c->d_items.alloc(c, (size_t)F * kMaxQuads * 2));
+  chk(c->d_refine.alloc(c, (size_t)F * kMaxQuads * 2 * rpp::kCand));
+  chk(c->d_jobs0.alloc(c, (size_t)F * kMaxQuads * 2));
+  chk(c->d_jobs1.alloc(c, (size_t)F * kMaxQuads * 2 * rpp::kCand));
+  chk(c->d_rq.alloc(c, 1));
   {
     // spill pools sized for the largest ObjPose grid objpose_blocks can return
     const size_t blocks = c->rpp_blocks > 0 ? (size_t)c->rpp_blocks : (size_t)std::max(64, 3 * c->n_cu / 2);
     c->op_cap = (int32_t)(blocks * 256);
     for (int k = 0; k < 2; k++) {
-      chk(dalloc(c, &c->d_opool[k], (size_t)kOpFields * c->op_cap));
-      chk(dalloc(c, &c->d_ojob[k], (size_t)c->op_cap));
+      chk(c->d_opool[k].alloc(c, (size_t)kOpFields * c->op_cap));
+      chk(c->d_ojob[k].alloc(c, (size_t)c->op_cap));
     }
-    chk(dalloc(c, &c->d_octl, 2 * 2 * kOpMaxRounds));
+    chk(c->d_octl.alloc(c, 2 * 2 * kOpMaxRounds));
   }
-  chk(dalloc(c, &c->d_gen, (size_t)F * kMaxHyps));
-  chk(dalloc(c, &c->d_hyps, (size_t)F * kMaxHyps));
-  chk(dalloc(c, &c->d_st, (size_t)F));
-  chk(dalloc(c, &c->d_sst, (size_t)F));
-  chk(dalloc(c, &c->d_dbg, (size_t)F));
-  chk(dalloc(c, &c->d_res, (size_t)F));
-  chk(dalloc(c, &c->d_gauss, (size_t)F * per));
+  chk(c->d_gen.alloc(c, (size_t)F * kMaxHyps));
+  chk(c->d_hyps.alloc(c, (size_t)F * kMaxHyps));
+  chk(c->d_st.alloc(c, (size_t)F));
+  chk(c->d_sst.alloc(c, (size_t)F));
+  chk(c->d_dbg.alloc(c, (size_t)F));
+  chk(c->d_res.alloc(c, (size_t)F));
+  chk(c->d_gauss.alloc(c, (size_t)F * per));
   c->gauss_cap = F;
-  chk(dalloc(c, &c->d_gtotal, 1));
-  chk(halloc(c, &c->h_gauss, (size_t)F * per));
-  chk(halloc(c, &c->h_states, (size_t)F + 1));
-  chk(halloc(c, &c->h_res, (size_t)F));
-  chk(halloc(c, &c->h_st, (size_t)F));
-  chk(halloc(c, &c->h_gtotal, 1));
-  chk(halloc(c, &c->h_frames, (size_t)F));
+  chk(c->d_gtotal.alloc(c, 1));
+  chk(c->h_gauss.alloc(c, (size_t)F * per));
+  chk(c->h_states.alloc(c, (size_t)F + 1));
+  chk(c->h_res.alloc(c, (size_t)F));
+  chk(c->h_st.alloc(c, (size_t)F));
+  chk(c->h_gtotal.alloc(c, 1));
+  chk(c->h_frames.alloc(c, (size_t)F));
   if (st != MANTIS_OK) {
     g_create_err = c->err;
     mantis_destroy(c);
@@ -1438,54 +1454,8 @@ mantis_status mantis_destroy(void* ctx) {
     if (g.pre) (void)hipGraphExecDestroy(g.pre);
     if (g.post) (void)hipGraphExecDestroy(g.post);
   }
-  if (c->d_rwjobs) (void)hipFree(c->d_rwjobs);
-  if (c->d_markov) (void)hipFree(c->d_markov);
-  if (c->d_mops) (void)hipFree(c->d_mops);
-  if (c->d_rwout) (void)hipFree(c->d_rwout);
-  void* dptrs[] = {c->d_opool[0], c->d_opool[1], c->d_ojob[0], c->d_ojob[1], c->d_octl, c->d_dense_jobs, c->d_agree, c->d_gn28, c->d_bgr, c->d_lroot, c->d_strong, c->d_edge, c->d_det, c->d_mask, c->d_lab, c->d_eb, c->d_b1, c->d_b2, c->d_mbits, c->d_dbits, c->d_tbits, c->d_rowb,
-                   c->d_frames, c->d_borders, c->d_bcount, c->d_boff, c->d_pool, c->d_scratch, c->d_quads, c->d_rpp, c->d_items, c->d_refine, c->d_jobs0, c->d_jobs1, c->d_rq,
-                   c->d_dense_c2w, c->d_dense_err, c->d_dense_np, c->d_pairs, c->d_gncam, c->d_rigio, c->d_gnobs, c->d_gnacc, c->d_sh_gidx, c->d_sh_pf, c->d_sh_flags, c->d_sh_rec, c->d_gen, c->d_hyps, c->d_st, c->d_sst, c->d_dbg, c->d_res, c->d_gauss, c->d_gtotal, c->d_lm};
-  for (void* p : dptrs)
-    if (p) (void)hipFree(p);
-  void* tptrs[] = {c->trk.d_in, c->trk.d_state, c->trk.d_res, c->trk.d_Twb, c->trk.d_c2w, c->trk.d_pf, c->trk.d_sums, c->trk.d_cnt};
-  for (void* p : tptrs)
-    if (p) (void)hipFree(p);
-  void* mptrs[] = {c->mcl.d_T[0], c->mcl.d_T[1], c->mcl.d_L, c->mcl.d_Lprev, c->mcl.d_q, c->mcl.d_cum, c->mcl.d_anc,
-                   c->mcl.d_in, c->mcl.d_c2w, c->mcl.d_pf, c->mcl.d_sums, c->mcl.d_cnt, c->mcl.d_res, c->mcl.d_modes, c->mcl.d_moved,
-                   c->mcl.d_csums, c->mcl.d_ccnt, c->mcl.d_Ec, c->mcl.d_charge};
-  for (void* p : mptrs)
-    if (p) (void)hipFree(p);
-  void* rptrs[] = {c->rf.d_cand, c->rf.d_gncam, c->rf.d_state, c->rf.d_recT, c->rf.d_recAcc, c->rf.d_slots,
-                   c->rf.d_rstats, c->rf.d_rkeys, c->rf.d_rweights};
-  for (void* p : rptrs)
-    if (p) (void)hipFree(p);
-  if (c->rf.h_state) (void)hipHostFree(c->rf.h_state);
-  if (c->rf.h_rstats) (void)hipHostFree(c->rf.h_rstats);
-  void* sptrs[] = {c->sm.d_out, c->sm.d_in, c->sm.d_work, c->sm.d_slots};
-  for (void* p : sptrs)
-    if (p) (void)hipFree(p);
-  if (c->sm.h_out) (void)hipHostFree(c->sm.h_out);
-  if (c->sm.h_in) (void)hipHostFree(c->sm.h_in);
-  for (Ctx::Linecal* k : {&c->cb, &c->ib, &c->rb}) {
-    void* kptrs[] = {k->d_state, k->d_T, k->d_acc, k->d_Y, k->d_Wt, k->d_cnt, k->d_pd,
-                     k->d_recT, k->d_recE, k->d_recKD, k->d_recAcc, k->d_slots,
-                     k->d_rkeys, k->d_rtab, k->d_rweights, k->d_rcells, k->d_rstats};
-    for (void* p : kptrs)
-      if (p) (void)hipFree(p);
-    if (k->h_state) (void)hipHostFree(k->h_state);
-    if (k->h_rstats) (void)hipHostFree(k->h_rstats);
-  }
   for (void* p : c->user_allocs) (void)hipFree(p);
-  void* hptrs[] = {c->h_gauss, c->h_states, c->h_res, c->h_st, c->h_gtotal, c->h_frames, c->h_sh_flags, c->h_sh_rec,
-                   c->trk.h_in, c->trk.h_res, c->mcl.h_in, c->mcl.h_res, c->mcl.h_modes, c->mcl.h_moved};
-  for (void* p : hptrs)
-    if (p) (void)hipHostFree(p);
-  for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-  if (c->ev_gauss) (void)hipEventDestroy(c->ev_gauss);
-  if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
-  if (c->s_copy) (void)hipStreamDestroy(c->s_copy);
-  if (c->s) (void)hipStreamDestroy(c->s);
-  delete c;
+  delete c;  // the members free the context's memory, then ~CtxStreams destroys the events and the streams
   return MANTIS_OK;
 }
 
@@ -1514,9 +1484,7 @@ mantis_status mantis_set_map(void* ctx, const double* white, int32_t nw, const d
   std::copy(all.begin(), all.end(), buf.begin());
   float* lf = (float*)(buf.data() + kLmfOffset);
   for (size_t i = 0; i < nl; i++) screen_landmark(all.data() + 3 * i, lf + 4 * i);
-  if (c->d_lm) (void)hipFree(c->d_lm);
-  c->d_lm = nullptr;
-  if (dalloc(c, &c->d_lm, buf.size()) != MANTIS_OK) return MANTIS_ERR_OOM;
+  if (c->d_lm.alloc(c, buf.size()) != MANTIS_OK) return MANTIS_ERR_OOM;
   HIP_OK(hipMemcpy(c->d_lm, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice));
   c->nw = nw;
   c->nr = nr;
@@ -1631,13 +1599,9 @@ mantis_status weight_rigs(Ctx* c, int n_rigs, int C, const mantis_cam_result* al
   const size_t need = std::max(nj, nslot);
   if (need > c->rw_cap) {
     HIP_OK(hipStreamSynchronize(c->s));
-    (void)hipFree(c->d_rwjobs);
-    (void)hipFree(c->d_rwout);
-    c->d_rwjobs = nullptr;
-    c->d_rwout = nullptr;
     c->rw_cap = 0;
     mantis_status st = MANTIS_OK;
-    if (dalloc(c, &c->d_rwjobs, need) || dalloc(c, &c->d_rwout, 2 * need)) st = MANTIS_ERR_OOM;
+    if (c->d_rwjobs.alloc(c, need) || c->d_rwout.alloc(c, 2 * need)) st = MANTIS_ERR_OOM;
     if (use_comm) st = agree(c, st);  // before the (sum, count) all-reduce
     if (st != MANTIS_OK) return st;
     c->rw_cap = need;
@@ -1782,17 +1746,11 @@ mantis_status mantis_process_rig_sharded(void* ctx, const mantis_image* local_ca
   if (vst == MANTIS_OK &&
       ((size_t)ng > c->sh_cap || (size_t)slots * (c->nranks + 1) * sizeof(ShardRec) > c->sh_rec_bytes)) {
     HIP_OK(hipStreamSynchronize(c->s));
-    void* d[] = {c->d_sh_gidx, c->d_sh_pf, c->d_sh_flags, c->d_sh_rec};
-    for (void* p : d) (void)hipFree(p);
-    void* h[] = {c->h_sh_flags, c->h_sh_rec};
-    for (void* p : h) (void)hipHostFree(p);
-    c->d_sh_gidx = c->d_sh_pf = c->d_sh_flags = c->h_sh_flags = nullptr;
-    c->d_sh_rec = c->h_sh_rec = nullptr;
     c->sh_cap = c->sh_rec_bytes = 0;
     const size_t rec_bytes = (size_t)slots * (c->nranks + 1) * sizeof(ShardRec);
-    if (dalloc(c, &c->d_sh_gidx, (size_t)ng) || dalloc(c, &c->d_sh_pf, (size_t)2 * ng * (c->nranks + 1)) ||
-        dalloc(c, &c->d_sh_flags, (size_t)2 * ng) || halloc(c, &c->h_sh_flags, (size_t)2 * ng) ||
-        dalloc(c, &c->d_sh_rec, rec_bytes) || halloc(c, &c->h_sh_rec, rec_bytes)) {
+    if (c->d_sh_gidx.alloc(c, (size_t)ng) || c->d_sh_pf.alloc(c, (size_t)2 * ng * (c->nranks + 1)) ||
+        c->d_sh_flags.alloc(c, (size_t)2 * ng) || c->h_sh_flags.alloc(c, (size_t)2 * ng) ||
+        c->d_sh_rec.alloc(c, rec_bytes) || c->h_sh_rec.alloc(c, rec_bytes)) {
       vst = MANTIS_ERR_OOM;
     } else {
       c->sh_cap = ng;
@@ -1809,7 +1767,7 @@ mantis_status mantis_process_rig_sharded(void* ctx, const mantis_image* local_ca
   if (st != MANTIS_OK && c->agreed_fail) return st;
   if ((st = agree(c, st)) != MANTIS_OK) return st;
   // gather every camera's result (one ncclAllGather of fixed-size records)
-  ShardRec* send = (ShardRec*)c->h_sh_rec;
+  ShardRec* send = (ShardRec*)c->h_sh_rec.get();
   for (int s = 0; s < slots; s++) {
     std::memset(&send[s], 0, sizeof(ShardRec));
     send[s].gidx = -1;
@@ -2110,9 +2068,8 @@ mantis_status mantis_score_hypotheses(void* ctx, const mantis_image* img, const 
   double* d_c2w = nullptr;
   double* d_err = nullptr;
   int32_t* d_np = nullptr;
-  if (dalloc(c, &d_c2w, (size_t)12 * n) != MANTIS_OK || dalloc(c, &d_err, (size_t)n) != MANTIS_OK ||
-      dalloc(c, &d_np, (size_t)n) != MANTIS_OK)
-    return MANTIS_ERR_OOM;
+  DevScratch ds(c);
+  if (ds.get(&d_c2w, (size_t)12 * n) || ds.get(&d_err, (size_t)n) || ds.get(&d_np, (size_t)n)) return MANTIS_ERR_OOM;
   const uint8_t* d_mask = nullptr;
   if (mask) {
     HIP_OK(hipMemcpyAsync(c->d_mask, mask, (size_t)W * H, hipMemcpyHostToDevice, c->s));
@@ -2128,9 +2085,6 @@ mantis_status mantis_score_hypotheses(void* ctx, const mantis_image* img, const 
   HIP_OK(hipMemcpyAsync(nproj, d_np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->s));
   HIP_OK(hipStreamSynchronize(c->s));
   finish_profile(c);
-  (void)hipFree(d_c2w);
-  (void)hipFree(d_err);
-  (void)hipFree(d_np);
   return MANTIS_OK;
 }
 
@@ -2141,8 +2095,9 @@ mantis_status mantis_quad_gn(void* ctx, const double* img_pts, const double* obj
   if (!c || !img_pts || !obj_pts || n <= 0 || !R || !t || iterations < 0 || iterations > 100) return MANTIS_ERR_ARG;
   double *d_ip, *d_op, *d_R, *d_t, *d_c;
   int32_t* d_s;
-  if (dalloc(c, &d_ip, (size_t)8 * n) || dalloc(c, &d_op, (size_t)12 * n) || dalloc(c, &d_R, (size_t)9 * n) ||
-      dalloc(c, &d_t, (size_t)3 * n) || dalloc(c, &d_c, (size_t)2 * n) || dalloc(c, &d_s, (size_t)n))
+  DevScratch ds(c);
+  if (ds.get(&d_ip, (size_t)8 * n) || ds.get(&d_op, (size_t)12 * n) || ds.get(&d_R, (size_t)9 * n) ||
+      ds.get(&d_t, (size_t)3 * n) || ds.get(&d_c, (size_t)2 * n) || ds.get(&d_s, (size_t)n))
     return MANTIS_ERR_OOM;
   HIP_OK(hipMemcpyAsync(d_ip, img_pts, sizeof(double) * 8 * n, hipMemcpyHostToDevice, c->s));
   HIP_OK(hipMemcpyAsync(d_op, obj_pts, sizeof(double) * 12 * n, hipMemcpyHostToDevice, c->s));
@@ -2155,8 +2110,6 @@ mantis_status mantis_quad_gn(void* ctx, const double* img_pts, const double* obj
   if (steps) HIP_OK(hipMemcpyAsync(steps, d_s, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->s));
   if (costs) HIP_OK(hipMemcpyAsync(costs, d_c, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->s));
   HIP_OK(hipStreamSynchronize(c->s));
-  void* ps[] = {d_ip, d_op, d_R, d_t, d_c, d_s};
-  for (void* p : ps) (void)hipFree(p);
   return MANTIS_OK;
 }
 
@@ -2171,9 +2124,10 @@ mantis_status mantis_rpp_batch(void* ctx, const double* img_pts, const double* o
   RppOut* d_out;
   int32_t *d_j0, *d_j1;
   RppQueue* d_q;
-  if (dalloc(c, &d_ip, (size_t)8 * n) || dalloc(c, &d_op, (size_t)12 * n) || dalloc(c, &d_it, (size_t)n) ||
-      dalloc(c, &d_rf, (size_t)n * rpp::kCand) || dalloc(c, &d_out, (size_t)n) || dalloc(c, &d_j0, (size_t)n) ||
-      dalloc(c, &d_j1, (size_t)n * rpp::kCand) || dalloc(c, &d_q, 1))
+  DevScratch ds(c);
+  if (ds.get(&d_ip, (size_t)8 * n) || ds.get(&d_op, (size_t)12 * n) || ds.get(&d_it, (size_t)n) ||
+      ds.get(&d_rf, (size_t)n * rpp::kCand) || ds.get(&d_out, (size_t)n) || ds.get(&d_j0, (size_t)n) ||
+      ds.get(&d_j1, (size_t)n * rpp::kCand) || ds.get(&d_q, 1))
     return MANTIS_ERR_OOM;
   HIP_OK(hipMemcpyAsync(d_ip, img_pts, sizeof(double) * 8 * n, hipMemcpyHostToDevice, c->s));
   HIP_OK(hipMemcpyAsync(d_op, obj_pts, sizeof(double) * 12 * n, hipMemcpyHostToDevice, c->s));
@@ -2194,8 +2148,6 @@ mantis_status mantis_rpp_batch(void* ctx, const double* img_pts, const double* o
     errs[2 * i + 1] = h[i].img_err;
     rpp_status[i] = h[i].error == 1 ? -1 : h[i].status;
   }
-  void* ps[] = {d_ip, d_op, d_it, d_rf, d_out, d_j0, d_j1, d_q};
-  for (void* p : ps) (void)hipFree(p);
   return MANTIS_OK;
 }
 
@@ -2247,7 +2199,8 @@ mantis_status mantis_synth_render(void* ctx, const mantis_synth_cam* cams, int32
   static_assert(sizeof(mantis_synth_cam) == sizeof(mantis_synth::Cam), "synth cam layout");
   mantis_synth::Cam* d_c;
   uint64_t* d_s;
-  if (dalloc(c, &d_c, (size_t)n) || dalloc(c, &d_s, (size_t)n)) return MANTIS_ERR_OOM;
+  DevScratch ds(c);
+  if (ds.get(&d_c, (size_t)n) || ds.get(&d_s, (size_t)n)) return MANTIS_ERR_OOM;
   HIP_OK(hipMemcpyAsync(d_c, cams, sizeof(mantis_synth::Cam) * n, hipMemcpyHostToDevice, c->s));
   HIP_OK(hipMemcpyAsync(d_s, seeds, sizeof(uint64_t) * n, hipMemcpyHostToDevice, c->s));
   size_t plane = (size_t)cams[0].w * cams[0].h * 3;
@@ -2255,8 +2208,6 @@ mantis_status mantis_synth_render(void* ctx, const mantis_synth_cam* cams, int32
   k_synth<<<g, 256, 0, c->s>>>(d_c, d_s, out_dev, plane);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(c->s));
-  (void)hipFree(d_c);
-  (void)hipFree(d_s);
   return MANTIS_OK;
 }
 

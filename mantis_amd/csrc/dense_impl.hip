@@ -119,6 +119,16 @@ mantis_status mantis_argmin_pick(const double* pairs, int32_t nranks, double* be
 }  // extern "C"
 
 namespace {
+// hypothesis, error and count buffers for `cap` hypotheses
+mantis_status dense_workspace(Ctx* c, size_t cap) {
+  if (cap <= c->dense_cap) return MANTIS_OK;
+  c->dense_cap = 0;
+  if (c->d_dense_c2w.alloc(c, 12 * cap) || c->d_dense_err.alloc(c, cap) || c->d_dense_np.alloc(c, cap))
+    return MANTIS_ERR_OOM;
+  c->dense_cap = cap;
+  return MANTIS_OK;
+}
+
 // dev: mask / c2w are device pointers read in place (mantis_score_argmin_dev)
 mantis_status score_argmin_impl(void* ctx, const mantis_image* img, const uint8_t* mask, const double* c2w,
                                 int32_t n, int64_t index_base, int32_t use_comm, double* best_err,
@@ -136,24 +146,8 @@ mantis_status score_argmin_impl(void* ctx, const mantis_image* img, const uint8_
     mantis_status st = stage_frames(c, img, 1, W, H);
     if (st != MANTIS_OK) return st;
     const size_t cap = (size_t)(n > 0 ? n : 1);
-    if (cap > c->dense_cap) {
-      (void)hipFree(c->d_dense_c2w);
-      (void)hipFree(c->d_dense_err);
-      (void)hipFree(c->d_dense_np);
-      c->d_dense_c2w = nullptr;
-      c->d_dense_err = nullptr;
-      c->d_dense_np = nullptr;
-      c->dense_cap = 0;
-      if (dalloc(c, &c->d_dense_c2w, 12 * cap) != MANTIS_OK || dalloc(c, &c->d_dense_err, cap) != MANTIS_OK ||
-          dalloc(c, &c->d_dense_np, cap) != MANTIS_OK)
-        return MANTIS_ERR_OOM;
-      c->dense_cap = cap;
-    }
-    if (!c->d_pairs) {
-      if (dalloc(c, &c->d_pairs, (size_t)2 * 64) != MANTIS_OK) return MANTIS_ERR_OOM;
-      c->dense_pairs_cap = 128;
-    }
-    return MANTIS_OK;
+    if (mantis_status e = dense_workspace(c, cap)) return e;
+    return c->d_pairs.grow(c, (size_t)2 * 64);
   };
   mantis_status st = prepare();
   if (use_comm) st = agree(c, st, 1);
@@ -228,42 +222,18 @@ mantis_status mantis_score_argmin_batch(void* ctx, const mantis_image* imgs, int
     }
     if (tot > (size_t)INT32_MAX) { c->err = "too many hypotheses in one batch"; return MANTIS_ERR_ARG; }
     const size_t cap = std::max<size_t>(tot, 1);
-    if (cap > c->dense_cap) {
-      (void)hipFree(c->d_dense_err);
-      (void)hipFree(c->d_dense_np);
-      (void)hipFree(c->d_dense_c2w);
-      c->d_dense_err = c->d_dense_c2w = nullptr;
-      c->d_dense_np = nullptr;
-      c->dense_cap = 0;
-      if (dalloc(c, &c->d_dense_c2w, 12 * cap) != MANTIS_OK || dalloc(c, &c->d_dense_err, cap) != MANTIS_OK ||
-          dalloc(c, &c->d_dense_np, cap) != MANTIS_OK)
-        return MANTIS_ERR_OOM;
-      c->dense_cap = cap;
-    }
+    if (mantis_status e = dense_workspace(c, cap)) return e;
     // at least the single-frame call's 64 pairs (mantis_score_argmin shares d_pairs)
     const size_t pair_cap = std::max<size_t>((size_t)2 * n_frames * (use_comm ? c->nranks + 1 : 1), 128);
-    if (pair_cap > c->dense_pairs_cap) {
-      (void)hipFree(c->d_pairs);
-      c->d_pairs = nullptr;
-      c->dense_pairs_cap = 0;
-      if (dalloc(c, &c->d_pairs, pair_cap) != MANTIS_OK) return MANTIS_ERR_OOM;
-      c->dense_pairs_cap = pair_cap;
-    }
     // the job table has its own capacity: d_pairs may already be large enough
     // (single-frame call) when the first batch arrives
-    if ((size_t)n_frames > c->dense_jobs_cap) {
-      (void)hipFree(c->d_dense_jobs);
-      c->d_dense_jobs = nullptr;
-      c->dense_jobs_cap = 0;
-      if (dalloc(c, (DenseJob**)&c->d_dense_jobs, (size_t)n_frames) != MANTIS_OK) return MANTIS_ERR_OOM;
-      c->dense_jobs_cap = (size_t)n_frames;
-    }
+    if (c->d_pairs.grow(c, pair_cap) || c->d_dense_jobs.grow(c, (size_t)n_frames)) return MANTIS_ERR_OOM;
     return MANTIS_OK;
   };
   mantis_status st = prepare();
   if (use_comm) st = agree(c, st, n_frames);
   if (st != MANTIS_OK) return st;
-  DenseJob* d_jobs = (DenseJob*)c->d_dense_jobs;
+  DenseJob* d_jobs = c->d_dense_jobs;
   HIP_OK(hipMemcpyAsync(d_jobs, jobs.data(), sizeof(DenseJob) * n_frames, hipMemcpyHostToDevice, c->s));
   Landmarks L = lmk_of(c);
   mark(c, "start");

@@ -283,16 +283,10 @@ mantis_status run_rig_gn(Ctx* c, const double* Tbc, int n_rigs, int cams_local, 
     }
   }
   if (c->gn_rigs < n_rigs || c->gn_cpr != cams_local) {
-    void* old[] = {c->d_gncam, c->d_rigio, c->d_gnobs, c->d_gnacc};
-    for (void* p : old) (void)hipFree(p);
-    c->d_gncam = nullptr;
-    c->d_rigio = nullptr;
-    c->d_gnobs = nullptr;
-    c->d_gnacc = nullptr;
     c->gn_rigs = 0;
     mantis_status st = MANTIS_OK;
-    if (dalloc(c, &c->d_gncam, (size_t)n) || dalloc(c, &c->d_rigio, (size_t)n_rigs) ||
-        dalloc(c, &c->d_gnobs, (size_t)n_rigs * obs_cap * 6) || dalloc(c, &c->d_gnacc, (size_t)n_rigs * kGnSlot))
+    if (c->d_gncam.alloc(c, (size_t)n) || c->d_rigio.alloc(c, (size_t)n_rigs) ||
+        c->d_gnobs.alloc(c, (size_t)n_rigs * obs_cap * 6) || c->d_gnacc.alloc(c, (size_t)n_rigs * kGnSlot))
       st = MANTIS_ERR_OOM;
     if (use_comm) st = agree(c, st);  // the other ranks would wait in the per-iteration all-reduce
     if (st != MANTIS_OK) return st;
@@ -372,8 +366,9 @@ mantis_status mantis_gn_accumulate(void* ctx, const double* T_w_b, const double*
   GnCam* d_c;
   double* d_o;
   double* d_out;
-  if (dalloc(c, &d_T, 16) || dalloc(c, &d_c, (size_t)n_cams) || dalloc(c, &d_o, (size_t)6 * std::max(n_obs, 1)) ||
-      dalloc(c, &d_out, 28))
+  DevScratch ds(c);
+  if (ds.get(&d_T, 16) || ds.get(&d_c, (size_t)n_cams) || ds.get(&d_o, (size_t)6 * std::max(n_obs, 1)) ||
+      ds.get(&d_out, 28))
     return MANTIS_ERR_OOM;
   HIP_OK(hipMemcpyAsync(d_T, T_w_b, sizeof(double) * 16, hipMemcpyHostToDevice, c->s));
   HIP_OK(hipMemcpyAsync(d_c, cams.data(), sizeof(GnCam) * n_cams, hipMemcpyHostToDevice, c->s));
@@ -382,8 +377,6 @@ mantis_status mantis_gn_accumulate(void* ctx, const double* T_w_b, const double*
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(acc28, d_out, sizeof(double) * 28, hipMemcpyDeviceToHost, c->s));
   HIP_OK(hipStreamSynchronize(c->s));
-  void* ps[] = {d_T, d_c, d_o, d_out};
-  for (void* p : ps) (void)hipFree(p);
   return MANTIS_OK;
 }
 
@@ -426,7 +419,7 @@ mantis_status mantis_comm_init(void* ctx, const void* id128, int32_t nranks, int
   }
   // the failure flag of the sharded call's agreement steps (agree(), api.hip):
   // allocated here so agreeing never needs an allocation
-  if (!c->d_agree && dalloc(c, &c->d_agree, 4) != MANTIS_OK) {
+  if (c->d_agree.grow(c, 4) != MANTIS_OK) {
     (void)ncclCommDestroy(comm);
     return MANTIS_ERR_OOM;
   }
@@ -473,7 +466,7 @@ mantis_status mantis_gn_allreduce(void* ctx, double* acc28) {
   if (c) bind_device(c);
   if (!c || !acc28) return MANTIS_ERR_ARG;
   if (!c->comm) { c->err = "comm not initialised (mantis_comm_init)"; return MANTIS_ERR_STATE; }
-  if (!c->d_gn28 && dalloc(c, &c->d_gn28, 28) != MANTIS_OK) return MANTIS_ERR_OOM;
+  if (c->d_gn28.grow(c, 28) != MANTIS_OK) return MANTIS_ERR_OOM;
   HIP_OK(hipMemcpyAsync(c->d_gn28, acc28, sizeof(double) * 28, hipMemcpyHostToDevice, c->s));
   ncclResult_t r = ncclAllReduce(c->d_gn28, c->d_gn28, 28, ncclFloat64, ncclSum, (ncclComm_t)c->comm, c->s);
   if (r != ncclSuccess) { c->err = std::string("ncclAllReduce: ") + ncclGetErrorString(r); return MANTIS_ERR_COMM; }

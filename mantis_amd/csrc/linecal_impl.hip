@@ -756,55 +756,32 @@ mantis_status linecal_workspace(Ctx* c, Ctx::Linecal& k, int N, int C, int I, bo
   const size_t slots = (record ? (size_t)I + 1 : 1) * N * C * std::max(c->rf.n_cand, 1);
   const size_t racc = record ? (size_t)(I + 1) * N * C * P::kAcc : 0;
   const size_t rkeys = robust ? slots : 0, rweights = robust && record ? slots : 0;
-  if (N > k.view_cap || slots > k.slot_cap || racc > k.racc_cap || rkeys > k.rkey_cap || rweights > k.rweight_cap ||
-      (robust && N > k.rcell_cap))
+  const size_t slot_bytes = slots * sizeof(typename P::Slot);
+  if (N > k.view_cap || slot_bytes > k.d_slots.capacity() || racc > k.d_recAcc.capacity() ||
+      rkeys > k.d_rkeys.capacity() || rweights > k.d_rweights.capacity() || (robust && N > k.rcell_cap))
     HIP_OK(hipStreamSynchronize(c->s));
   if (N > k.view_cap) {
     k.view_cap = 0;
-    if (k.h_state) (void)hipHostFree(k.h_state);
-    k.h_state = nullptr;
     const size_t n = (size_t)N, nc = n * lc::kMaxCams;
     // pinned: the state, the poses, the accumulators, the counts
     const size_t hb = sizeof(mk::LinecalState) + sizeof(double) * (16 * n + P::kAcc * nc) + sizeof(int32_t) * nc;
-    if (refine_grow(c, (mk::LinecalState**)&k.d_state, (size_t)1) || refine_grow(c, &k.d_T, 16 * n) ||
-        refine_grow(c, &k.d_acc, P::kAcc * nc) || refine_grow(c, &k.d_cnt, nc) ||
-        refine_grow(c, &k.d_Y, n * 6 * P::kLd) || refine_grow(c, &k.d_Wt, n * P::kMaxS * P::kLd) ||
-        refine_grow(c, &k.d_pd, n) || refine_grow(c, &k.d_recT, (size_t)(rfn::kMaxIterations + 1) * 16 * n) ||
-        (P::kExt && refine_grow(c, &k.d_recE, (size_t)(rfn::kMaxIterations + 1) * 16 * lc::kMaxCams)) ||
-        (P::kInt && refine_grow(c, &k.d_recKD, (size_t)(rfn::kMaxIterations + 1) * lc::kPi * lc::kMaxCams)) ||
-        halloc(c, (uint8_t**)&k.h_state, hb))
+    if (k.d_state.alloc(c, 1) || k.d_T.alloc(c, 16 * n) || k.d_acc.alloc(c, P::kAcc * nc) || k.d_cnt.alloc(c, nc) ||
+        k.d_Y.alloc(c, n * 6 * P::kLd) || k.d_Wt.alloc(c, n * P::kMaxS * P::kLd) || k.d_pd.alloc(c, n) ||
+        k.d_recT.alloc(c, (size_t)(rfn::kMaxIterations + 1) * 16 * n) ||
+        (P::kExt && k.d_recE.alloc(c, (size_t)(rfn::kMaxIterations + 1) * 16 * lc::kMaxCams)) ||
+        (P::kInt && k.d_recKD.alloc(c, (size_t)(rfn::kMaxIterations + 1) * lc::kPi * lc::kMaxCams)) ||
+        k.h_state.alloc(c, hb))
       return MANTIS_ERR_OOM;
     k.view_cap = N;
   }
-  if (slots > k.slot_cap) {
-    k.slot_cap = 0;
-    if (refine_grow(c, (typename P::Slot**)&k.d_slots, slots)) return MANTIS_ERR_OOM;
-    k.slot_cap = slots;
-  }
-  if (racc > k.racc_cap) {
-    k.racc_cap = 0;
-    if (refine_grow(c, &k.d_recAcc, racc)) return MANTIS_ERR_OOM;
-    k.racc_cap = racc;
-  }
-  if (rkeys > k.rkey_cap) {
-    k.rkey_cap = 0;
-    if (refine_grow(c, &k.d_rkeys, rkeys)) return MANTIS_ERR_OOM;
-    k.rkey_cap = rkeys;
-  }
-  if (rweights > k.rweight_cap) {
-    k.rweight_cap = 0;
-    if (refine_grow(c, &k.d_rweights, rweights)) return MANTIS_ERR_OOM;
-    k.rweight_cap = rweights;
-  }
+  if (k.d_slots.grow(c, slot_bytes) || k.d_recAcc.grow(c, racc) || k.d_rkeys.grow(c, rkeys) ||
+      k.d_rweights.grow(c, rweights))
+    return MANTIS_ERR_OOM;
   if (robust && N > k.rcell_cap) {
     k.rcell_cap = 0;
-    if (k.h_rstats) (void)hipHostFree(k.h_rstats);
-    k.h_rstats = nullptr;
-    if (refine_grow(c, (lc::RobustCell**)&k.d_rcells, (size_t)N * lc::kMaxCams) ||
-        refine_grow(c, &k.d_rtab, (size_t)(rfn::kMaxIterations + 1) * mk::kLinecalTab) ||
-        refine_grow(c, &k.d_rstats, (size_t)1) || halloc(c, (uint8_t**)&k.h_rstats,
-                                                      sizeof(mantis_calib_robust_stats) +
-                                                          sizeof(lc::RobustCell) * (size_t)N * lc::kMaxCams))
+    if (k.d_rcells.alloc(c, (size_t)N * lc::kMaxCams) ||
+        k.d_rtab.alloc(c, (size_t)(rfn::kMaxIterations + 1) * mk::kLinecalTab) || k.d_rstats.alloc(c, 1) ||
+        k.h_rstats.alloc(c, sizeof(mantis_calib_robust_stats) + sizeof(lc::RobustCell) * (size_t)N * lc::kMaxCams))
       return MANTIS_ERR_OOM;
     k.rcell_cap = N;
   }
@@ -840,7 +817,8 @@ mantis_status linecal_run(Ctx* c, Ctx::Linecal& k, const LinecalNames& nm, const
   if (mantis_status e = linecal_workspace<P>(c, k, N, C, I, p->record != 0, kR)) return e;
   const int nc = c->rf.n_cand;
 
-  mk::LinecalState* h_st = (mk::LinecalState*)k.h_state;
+  mk::LinecalState* h_st = (mk::LinecalState*)k.h_state.get();
+  mantis_calib_robust_stats* h_rstats = (mantis_calib_robust_stats*)k.h_rstats.get();  // null with the robust rows never on
   double* h_T = (double*)(h_st + 1);
   double* h_acc = h_T + 16 * (size_t)k.view_cap;
   int32_t* h_cnt = (int32_t*)(h_acc + (size_t)P::kAcc * k.view_cap * lc::kMaxCams);
@@ -933,8 +911,8 @@ mantis_status linecal_run(Ctx* c, Ctx::Linecal& k, const LinecalNames& nm, const
     mark(c, nm.solve);
   }
   if constexpr (kR) {  // the stats, and behind them the cells of the last pass run (for the gate)
-    HIP_OK(hipMemcpyAsync(k.h_rstats, k.d_rstats, sizeof(mantis_calib_robust_stats), hipMemcpyDeviceToHost, c->s));
-    HIP_OK(hipMemcpyAsync(k.h_rstats + 1, k.d_rcells, sizeof(lc::RobustCell) * (size_t)n, hipMemcpyDeviceToHost, c->s));
+    HIP_OK(hipMemcpyAsync(h_rstats, k.d_rstats, sizeof(mantis_calib_robust_stats), hipMemcpyDeviceToHost, c->s));
+    HIP_OK(hipMemcpyAsync(h_rstats + 1, k.d_rcells, sizeof(lc::RobustCell) * (size_t)n, hipMemcpyDeviceToHost, c->s));
   }
   HIP_OK(hipMemcpyAsync(h_st, k.d_state, mk::kLinecalStateBytes, hipMemcpyDeviceToHost, c->s));
   HIP_OK(hipMemcpyAsync(h_T, k.d_T, sizeof(double) * 16 * (size_t)N, hipMemcpyDeviceToHost, c->s));
@@ -945,12 +923,12 @@ mantis_status linecal_run(Ctx* c, Ctx::Linecal& k, const LinecalNames& nm, const
   k.rec_loss = kR ? c->calib_robust.loss : 0;
   if constexpr (kR) {
     std::vector<int32_t> pos((size_t)n);  // the rows with w > 0 of the last pass run
-    lc::robust_pos((const lc::RobustCell*)(k.h_rstats + 1), h_cnt, n, pos.data());
+    lc::robust_pos((const lc::RobustCell*)(h_rstats + 1), h_cnt, n, pos.data());
     P::conclude(h_acc, h_cnt, N, C, fe, fi, pm, p->min_obs, min_obs_cam, p->max_rms, h_st->res, pos.data());
-    k.h_rstats->loss = c->calib_robust.loss;
-    k.h_rstats->kind = P::kExt && P::kInt ? lc::kKindRig : P::kInt ? lc::kKindInt : lc::kKindExt;
-    k.h_rstats->n_rigs = N;
-    k.h_rstats->n_cams = C;
+    h_rstats->loss = c->calib_robust.loss;
+    h_rstats->kind = P::kExt && P::kInt ? lc::kKindRig : P::kInt ? lc::kKindInt : lc::kKindExt;
+    h_rstats->n_rigs = N;
+    h_rstats->n_cams = C;
   } else {
     P::conclude(h_acc, h_cnt, N, C, fe, fi, pm, p->min_obs, min_obs_cam, p->max_rms, h_st->res);
   }
@@ -984,7 +962,7 @@ mantis_status linecal_record(Ctx* c, const Ctx::Linecal& k, const LinecalNames& 
     HIP_OK(hipMemcpy(KD, k.d_recKD + (size_t)pass * k.C * lc::kPi, sizeof(double) * lc::kPi * k.C, hipMemcpyDeviceToHost));
   if (acc)
     HIP_OK(hipMemcpy(acc, k.d_recAcc + pr * k.C * P::kAcc, sizeof(double) * P::kAcc * k.C, hipMemcpyDeviceToHost));
-  return slots_scatter<Slot, P::kRow>(c, (const Slot*)k.d_slots + pr * ns, ns, codes, Sw, Skw, rows);
+  return slots_scatter<Slot, P::kRow>(c, (const Slot*)k.d_slots.get() + pr * ns, ns, codes, Sw, Skw, rows);
 }
 
 // ---- the three entry points: each its own validation, then the one driver ----
@@ -1235,7 +1213,7 @@ mantis_status mantis_get_calib_robust(void* ctx, int32_t kind, mantis_calib_robu
     c->err = "calib robust: no calibration of that kind yet, or its last call ran with the robust rows off";
     return MANTIS_ERR_STATE;
   }
-  *stats = *k.h_rstats;
+  *stats = *(const mantis_calib_robust_stats*)k.h_rstats.get();
   return MANTIS_OK;
 }
 

@@ -103,7 +103,7 @@ void markov_gauss(MarkovOp& op, double stddev) {
 
 mantis_status markov_run(Ctx* c, std::vector<MarkovOp>& ops) {
   const int n = c->markov_n;
-  if (!c->d_mops && dalloc(c, &c->d_mops, (size_t)n) != MANTIS_OK) return MANTIS_ERR_OOM;
+  if (c->d_mops.grow(c, (size_t)n) != MANTIS_OK) return MANTIS_ERR_OOM;
   HIP_OK(hipMemcpyAsync(c->d_mops, ops.data(), sizeof(MarkovOp) * n, hipMemcpyHostToDevice, c->s));
   k_markov<<<n, 384, 0, c->s>>>(c->d_markov, c->d_mops);
   HIP_OK(hipGetLastError());
@@ -121,12 +121,9 @@ mantis_status mantis_markov_init(void* ctx, int32_t n_filters, const double* w2c
   if (!c || n_filters <= 0 || n_filters > (1 << 20) || !w2c_R) return MANTIS_ERR_ARG;
   if (n_filters != c->markov_n) {
     HIP_OK(hipStreamSynchronize(c->s));
-    (void)hipFree(c->d_markov);
-    (void)hipFree(c->d_mops);
-    c->d_markov = nullptr;
-    c->d_mops = nullptr;
+    c->d_mops.release();
     c->markov_n = 0;
-    if (dalloc(c, &c->d_markov, (size_t)n_filters * mk::kYawBins) != MANTIS_OK) return MANTIS_ERR_OOM;
+    if (c->d_markov.alloc(c, (size_t)n_filters * mk::kYawBins) != MANTIS_OK) return MANTIS_ERR_OOM;
     c->markov_n = n_filters;
   }
   std::vector<MarkovOp> ops(n_filters);
@@ -181,15 +178,8 @@ mantis_status mantis_markov_weight(void* ctx, int32_t filter, const double* w2c_
   for (int h = 0; h < n; h++) bins[h] = markov_bin(w2c_R + 9 * (size_t)h);
   int32_t* d_b = nullptr;
   double* d_e = nullptr;
-  struct Free {  // the temporaries are freed on every path (also the HIP_OK early returns)
-    int32_t*& b;
-    double*& e;
-    ~Free() {
-      (void)hipFree(b);
-      (void)hipFree(e);
-    }
-  } fr{d_b, d_e};
-  if (dalloc(c, &d_b, (size_t)n) || dalloc(c, &d_e, (size_t)n)) return MANTIS_ERR_OOM;
+  DevScratch ds(c);
+  if (ds.get(&d_b, (size_t)n) || ds.get(&d_e, (size_t)n)) return MANTIS_ERR_OOM;
   HIP_OK(hipMemcpyAsync(d_b, bins.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, c->s));
   HIP_OK(hipMemcpyAsync(d_e, error, sizeof(double) * n, hipMemcpyHostToDevice, c->s));
   k_markov_weight<<<(n + 255) / 256, 256, 0, c->s>>>(c->d_markov + (size_t)filter * mk::kYawBins, d_b, n, d_e);

@@ -201,8 +201,7 @@ mantis_status mcl_color_workspace(Ctx* c) {
   HIP_OK(hipStreamSynchronize(c->s));  // nothing of an earlier step still reads what is freed
   m.color_cap = 0;
   const size_t n = (size_t)m.cap, tasks = n * mk::track::kMaxCams;
-  if (mcl_grow(c, &m.d_csums, tasks) || mcl_grow(c, &m.d_ccnt, tasks) || mcl_grow(c, &m.d_Ec, n) ||
-      mcl_grow(c, &m.d_charge, n))
+  if (m.d_csums.alloc(c, tasks) || m.d_ccnt.alloc(c, tasks) || m.d_Ec.alloc(c, n) || m.d_charge.alloc(c, n))
     return MANTIS_ERR_OOM;
   m.color_cap = m.cap;
   return MANTIS_OK;

@@ -298,13 +298,6 @@ mantis_status mcl_check_params(Ctx* c, const mantis_mcl_params* p) {
   return MANTIS_OK;
 }
 
-template <class T>
-mantis_status mcl_grow(Ctx* c, T** p, size_t count) {
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  return dalloc(c, p, count);
-}
-
 // buffers for N particles (x 8 cameras); an init with more particles than any before reallocates
 mantis_status mcl_workspace(Ctx* c, int N) {
   Ctx::Mcl& m = c->mcl;
@@ -315,15 +308,10 @@ mantis_status mcl_workspace(Ctx* c, int N) {
   m.has_record = m.has_modes = false;
   const size_t n = (size_t)N, tasks = n * mk::track::kMaxCams;
   const size_t in_bytes = sizeof(Xf) * (mk::track::kMaxCams + 1) + sizeof(float) * n * 6;
-  if (m.h_in) (void)hipHostFree(m.h_in);
-  if (m.h_res) (void)hipHostFree(m.h_res);
-  m.h_in = m.h_res = nullptr;
-  if (mcl_grow(c, (Xf**)&m.d_T[0], n) || mcl_grow(c, (Xf**)&m.d_T[1], n) || mcl_grow(c, &m.d_L, n) ||
-      mcl_grow(c, &m.d_Lprev, n) || mcl_grow(c, &m.d_q, n) || mcl_grow(c, &m.d_cum, n) || mcl_grow(c, &m.d_anc, n) ||
-      mcl_grow(c, (uint8_t**)&m.d_in, in_bytes) || halloc(c, (uint8_t**)&m.h_in, in_bytes) ||
-      mcl_grow(c, (Xf**)&m.d_c2w, tasks) || mcl_grow(c, (PoseF**)&m.d_pf, tasks) || mcl_grow(c, &m.d_sums, tasks) ||
-      mcl_grow(c, &m.d_cnt, tasks) || mcl_grow(c, (mantis_mcl_result**)&m.d_res, (size_t)1) ||
-      halloc(c, (mantis_mcl_result**)&m.h_res, (size_t)1))
+  if (m.d_T[0].alloc(c, n) || m.d_T[1].alloc(c, n) || m.d_L.alloc(c, n) || m.d_Lprev.alloc(c, n) ||
+      m.d_q.alloc(c, n) || m.d_cum.alloc(c, n) || m.d_anc.alloc(c, n) || m.d_in.alloc(c, in_bytes) ||
+      m.h_in.alloc(c, in_bytes) || m.d_c2w.alloc(c, tasks) || m.d_pf.alloc(c, tasks) || m.d_sums.alloc(c, tasks) ||
+      m.d_cnt.alloc(c, tasks) || m.d_res.alloc(c, 1) || m.h_res.alloc(c, 1))
     return MANTIS_ERR_OOM;
   m.cap = N;
   return MANTIS_OK;
@@ -458,7 +446,7 @@ mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cam
   }
 
   // inputs in one pinned block: extrinsics (8 slots), the motion, the gaussians in draw order
-  Xf* h_ext = (Xf*)m.h_in;
+  Xf* h_ext = (Xf*)m.h_in.get();
   Xf* h_delta = h_ext + mk::track::kMaxCams;
   float* h_g = (float*)(h_delta + 1);
   for (int i = 0; i < C; i++) h_ext[i] = mk::track::xf_from_mat4(cams[i].T_base_cam);
@@ -489,7 +477,7 @@ mantis_status mantis_mcl_step(void* ctx, const mantis_image* cams, int32_t n_cam
   mk::MclArgs a;
   a.T = (Xf*)m.d_T[m.cur];
   a.Tdst = (Xf*)m.d_T[m.cur ^ 1];
-  a.ext = (const Xf*)m.d_in;
+  a.ext = (const Xf*)m.d_in.get();
   a.delta = a.ext + mk::track::kMaxCams;
   a.gauss = (const float*)(a.delta + 1);
   a.L = m.d_L;

@@ -271,9 +271,8 @@ mantis_status mcl_state(Ctx* c, const char* what) {
 // the result buffers of the two calls: the modes record and the kept count behind it
 mantis_status mcl_modes_buffers(Ctx* c) {
   Ctx::Mcl& m = c->mcl;
-  if (m.d_modes && m.h_modes) return MANTIS_OK;
   const size_t bytes = sizeof(mcl_modes_rec) + 16;
-  if (dalloc(c, (uint8_t**)&m.d_modes, bytes) || halloc(c, (uint8_t**)&m.h_modes, bytes)) return MANTIS_ERR_OOM;
+  if (m.d_modes.grow(c, bytes) || m.h_modes.grow(c, bytes)) return MANTIS_ERR_OOM;
   return MANTIS_OK;
 }
 
@@ -342,7 +341,7 @@ mantis_status mantis_mcl_modes(void* ctx, int32_t max_modes, struct mantis_mcl_m
     a.q = m.d_q;
     a.sums = m.d_sums;
     a.cnt = m.d_cnt;
-    a.out = (mc::Modes*)m.d_modes;
+    a.out = (mc::Modes*)m.d_modes.get();
     a.N = m.N;
     a.C = m.rec_C;
     a.best = last.best;

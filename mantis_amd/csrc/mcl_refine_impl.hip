@@ -59,8 +59,7 @@ namespace {
 
 mantis_status mcl_refine_buffers(Ctx* c) {
   Ctx::Mcl& m = c->mcl;
-  if (m.d_moved && m.h_moved) return MANTIS_OK;
-  if (dalloc(c, &m.d_moved, (size_t)mc::kMaxModes) || halloc(c, &m.h_moved, (size_t)mc::kMaxModes)) return MANTIS_ERR_OOM;
+  if (m.d_moved.grow(c, (size_t)mc::kMaxModes) || m.h_moved.grow(c, (size_t)mc::kMaxModes)) return MANTIS_ERR_OOM;
   return MANTIS_OK;
 }
 

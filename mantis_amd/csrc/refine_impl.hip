@@ -237,13 +237,6 @@ mantis_status slots_scatter(Ctx* c, const S* d_slots, size_t ns, int32_t* codes,
   return MANTIS_OK;
 }
 
-template <class T>
-mantis_status refine_grow(Ctx* c, T** p, size_t count) {
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  return dalloc(c, p, count);
-}
-
 // the line flags of the current map at `pitch`, and the candidate list on the device
 mantis_status refine_flags(Ctx* c, double pitch) {
   Ctx::Refine& r = c->rf;
@@ -255,11 +248,7 @@ mantis_status refine_flags(Ctx* c, double pitch) {
   std::vector<int32_t> cand(n > 0 ? n : 1);
   r.n_cand = rfn::candidates(r.flags.data(), n, cand.data());
   HIP_OK(hipStreamSynchronize(c->s));  // nothing of an earlier call still reads the list
-  if (r.n_cand > r.cand_cap) {
-    r.cand_cap = 0;
-    if (refine_grow(c, &r.d_cand, (size_t)r.n_cand)) return MANTIS_ERR_OOM;
-    r.cand_cap = r.n_cand;
-  }
+  if (r.d_cand.grow(c, (size_t)r.n_cand)) return MANTIS_ERR_OOM;
   if (r.n_cand > 0) HIP_OK(hipMemcpy(r.d_cand, cand.data(), sizeof(int32_t) * r.n_cand, hipMemcpyHostToDevice));
   r.pitch = pitch;
   return MANTIS_OK;
@@ -270,41 +259,24 @@ mantis_status refine_workspace(Ctx* c, int R, int C, int F, int I, bool record, 
   Ctx::Refine& r = c->rf;
   const size_t slots = (record ? (size_t)I + 1 : 1) * R * C * std::max(r.n_cand, 1);
   const size_t rslots = robust && record ? slots : 0;  // keys and weights: only as a record
-  if (R > r.rig_cap || F > r.cam_cap || slots > r.slot_cap || rslots > r.rslot_cap || (robust && R > r.rstat_cap))
+  const size_t rstats = robust ? (size_t)R : 0;
+  if (R > r.rig_cap || F > r.cam_cap || slots > r.d_slots.capacity() || rslots > r.d_rkeys.capacity() ||
+      rstats > r.d_rstats.capacity())
     HIP_OK(hipStreamSynchronize(c->s));
   if (R > r.rig_cap || F > r.cam_cap) {
     const int rc = std::max(R, r.rig_cap), cc = std::max(F, r.cam_cap);
     r.rig_cap = r.cam_cap = 0;
-    if (r.h_state) (void)hipHostFree(r.h_state);
-    r.h_state = nullptr;
     const size_t hb = sizeof(mk::RefineRig) * rc + sizeof(mk::GnCam) * cc;
-    if (refine_grow(c, (mk::RefineRig**)&r.d_state, (size_t)rc) || refine_grow(c, (mk::GnCam**)&r.d_gncam, (size_t)cc) ||
-        refine_grow(c, &r.d_recT, (size_t)(rfn::kMaxIterations + 1) * rc * 16) ||
-        refine_grow(c, &r.d_recAcc, (size_t)(rfn::kMaxIterations + 1) * rc * 28) ||
-        halloc(c, (uint8_t**)&r.h_state, hb))
+    if (r.d_state.alloc(c, (size_t)rc) || r.d_gncam.alloc(c, (size_t)cc) ||
+        r.d_recT.alloc(c, (size_t)(rfn::kMaxIterations + 1) * rc * 16) ||
+        r.d_recAcc.alloc(c, (size_t)(rfn::kMaxIterations + 1) * rc * 28) || r.h_state.alloc(c, hb))
       return MANTIS_ERR_OOM;
     r.rig_cap = rc;
     r.cam_cap = cc;
   }
-  if (slots > r.slot_cap) {
-    r.slot_cap = 0;
-    if (refine_grow(c, (rfn::Slot**)&r.d_slots, slots)) return MANTIS_ERR_OOM;
-    r.slot_cap = slots;
-  }
-  if (robust && R > r.rstat_cap) {
-    r.rstat_cap = 0;
-    if (r.h_rstats) (void)hipHostFree(r.h_rstats);
-    r.h_rstats = nullptr;
-    if (refine_grow(c, &r.d_rstats, (size_t)R) ||
-        halloc(c, (uint8_t**)&r.h_rstats, sizeof(mantis_refine_robust_stats) * R))
-      return MANTIS_ERR_OOM;
-    r.rstat_cap = R;
-  }
-  if (rslots > r.rslot_cap) {
-    r.rslot_cap = 0;
-    if (refine_grow(c, &r.d_rkeys, rslots) || refine_grow(c, &r.d_rweights, rslots)) return MANTIS_ERR_OOM;
-    r.rslot_cap = rslots;
-  }
+  if (r.d_slots.grow(c, slots) || r.d_rstats.grow(c, rstats) || r.h_rstats.grow(c, rstats) ||
+      r.d_rkeys.grow(c, rslots) || r.d_rweights.grow(c, rslots))
+    return MANTIS_ERR_OOM;
   return MANTIS_OK;
 }
 
@@ -363,7 +335,7 @@ mantis_status refine_run(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32
   if (mantis_status e = refine_flags(c, p->landmark_pitch)) return e;
   if (mantis_status e = refine_workspace(c, n_rigs, C, n, I, p->record != 0, robust)) return e;
 
-  mk::RefineRig* h_st = (mk::RefineRig*)r.h_state;
+  mk::RefineRig* h_st = (mk::RefineRig*)r.h_state.get();
   mk::GnCam* h_gc = (mk::GnCam*)(h_st + r.rig_cap);
   for (int k = 0; k < n_rigs; k++) {
     std::memset(&h_st[k], 0, sizeof(h_st[k]));

@@ -298,32 +298,12 @@ SmoothLayout smooth_layout(size_t V, size_t Wn, size_t F, size_t P) {
 
 mantis_status smooth_workspace(Ctx* c, const SmoothLayout& L, size_t slots) {
   Ctx::Smooth& r = c->sm;
-  if (L.out_bytes > r.out_cap || L.in_bytes > r.in_cap || L.work_doubles > r.work_cap || slots > r.slot_cap)
+  if (L.out_bytes > r.d_out.capacity() || L.in_bytes > r.d_in.capacity() || L.work_doubles > r.d_work.capacity() ||
+      slots > r.d_slots.capacity())
     HIP_OK(hipStreamSynchronize(c->s));
-  if (L.out_bytes > r.out_cap) {
-    r.out_cap = 0;
-    if (r.h_out) (void)hipHostFree(r.h_out);
-    r.h_out = nullptr;
-    if (refine_grow(c, &r.d_out, L.out_bytes) || halloc(c, &r.h_out, L.out_bytes)) return MANTIS_ERR_OOM;
-    r.out_cap = L.out_bytes;
-  }
-  if (L.in_bytes > r.in_cap) {
-    r.in_cap = 0;
-    if (r.h_in) (void)hipHostFree(r.h_in);
-    r.h_in = nullptr;
-    if (refine_grow(c, &r.d_in, L.in_bytes) || halloc(c, &r.h_in, L.in_bytes)) return MANTIS_ERR_OOM;
-    r.in_cap = L.in_bytes;
-  }
-  if (L.work_doubles > r.work_cap) {
-    r.work_cap = 0;
-    if (refine_grow(c, &r.d_work, L.work_doubles)) return MANTIS_ERR_OOM;
-    r.work_cap = L.work_doubles;
-  }
-  if (slots > r.slot_cap) {
-    r.slot_cap = 0;
-    if (refine_grow(c, (rfn::Slot**)&r.d_slots, slots)) return MANTIS_ERR_OOM;
-    r.slot_cap = slots;
-  }
+  if (r.d_out.grow(c, L.out_bytes) || r.h_out.grow(c, L.out_bytes) || r.d_in.grow(c, L.in_bytes) ||
+      r.h_in.grow(c, L.in_bytes) || r.d_work.grow(c, L.work_doubles) || r.d_slots.grow(c, slots))
+    return MANTIS_ERR_OOM;
   return MANTIS_OK;
 }
 
@@ -377,7 +357,7 @@ mantis_status smooth_impl(Ctx* c, const mantis_image* cams, int32_t Wn, int32_t 
     return e;
 
   std::memset(r.h_out, 0, L.o_Hd);
-  mk::RefineRig* h_st = (mk::RefineRig*)r.h_out;
+  mk::RefineRig* h_st = (mk::RefineRig*)r.h_out.get();
   mk::SmoothWin* h_win = (mk::SmoothWin*)(r.h_out + L.o_win);
   for (int k = 0; k < V; k++) {
     std::memcpy(h_st[k].res.T_w_b, T_in + 16 * (size_t)k, sizeof(double) * 16);
@@ -389,7 +369,7 @@ mantis_status smooth_impl(Ctx* c, const mantis_image* cams, int32_t Wn, int32_t 
     h_win[w].res.has_prior = prior_T ? 1 : 0;
   }
   std::memset(r.h_in, 0, L.in_bytes);
-  double* h_D = (double*)r.h_in;
+  double* h_D = (double*)r.h_in.get();
   int32_t* h_has = (int32_t*)(r.h_in + L.i_has);
   for (int w = 0; w < Wn; w++)
     for (int k = 0; k < N - 1; k++) {
@@ -416,7 +396,7 @@ mantis_status smooth_impl(Ctx* c, const mantis_image* cams, int32_t Wn, int32_t 
   mk::RefineArgs a;
   a.gncam = (const mk::GnCam*)(r.d_in + L.i_gncam);
   a.cand = rf.d_cand;
-  a.st = (mk::RefineRig*)r.d_out;
+  a.st = (mk::RefineRig*)r.d_out.get();
   a.slots = (rfn::Slot*)r.d_slots;
   a.recT = r.d_work + L.w_recT;
   a.recAcc = r.d_work + L.w_recAcc;
@@ -431,7 +411,7 @@ mantis_status smooth_impl(Ctx* c, const mantis_image* cams, int32_t Wn, int32_t 
   a.lambda = p->lambda;
   mk::SmoothArgs s;
   s.win = (mk::SmoothWin*)(r.d_out + L.o_win);
-  s.D = (const double*)r.d_in;
+  s.D = (const double*)r.d_in.get();
   s.has = (const int32_t*)(r.d_in + L.i_has);
   s.Tp = (const double*)(r.d_in + L.i_Tp);
   s.Wp = (const double*)(r.d_in + L.i_Wp);

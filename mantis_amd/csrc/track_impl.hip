@@ -138,49 +138,19 @@ namespace {
 
 namespace trk = mk::track;
 
-template <class T>
-mantis_status track_grow(Ctx* c, T** p, size_t count) {
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  return dalloc(c, p, count);
-}
-
 // workspaces for a call of R rigs x C cameras x P particles x I iterations
 mantis_status track_workspace(Ctx* c, int R, int C, int P, int I, bool record) {
   Ctx::Track& t = c->trk;
   const size_t in_bytes = sizeof(Xf) * ((size_t)R + (size_t)R * C) + sizeof(float) * (size_t)R * I * P * 6;
   const size_t passes = record ? (size_t)I + 1 : 1;
   const size_t poses = passes * R * P, tasks = poses * C;
-  if (in_bytes > t.in_cap || R > t.rig_cap || poses > t.pose_cap || tasks > t.task_cap)
+  if (in_bytes > t.d_in.capacity() || (size_t)R > t.d_state.capacity() || poses > t.d_Twb.capacity() ||
+      tasks > t.d_c2w.capacity())
     HIP_OK(hipStreamSynchronize(c->s));  // nothing of an earlier call still reads what is freed
-  if (in_bytes > t.in_cap) {
-    t.in_cap = 0;
-    if (t.h_in) (void)hipHostFree(t.h_in);
-    t.h_in = nullptr;
-    if (track_grow(c, (uint8_t**)&t.d_in, in_bytes) || halloc(c, (uint8_t**)&t.h_in, in_bytes)) return MANTIS_ERR_OOM;
-    t.in_cap = in_bytes;
-  }
-  if (R > t.rig_cap) {
-    t.rig_cap = 0;
-    if (t.h_res) (void)hipHostFree(t.h_res);
-    t.h_res = nullptr;
-    if (track_grow(c, (TrackState**)&t.d_state, (size_t)R) || track_grow(c, (mantis_track_result**)&t.d_res, (size_t)R) ||
-        halloc(c, (mantis_track_result**)&t.h_res, (size_t)R))
-      return MANTIS_ERR_OOM;
-    t.rig_cap = R;
-  }
-  if (poses > t.pose_cap) {
-    t.pose_cap = 0;
-    if (track_grow(c, (Xf**)&t.d_Twb, poses)) return MANTIS_ERR_OOM;
-    t.pose_cap = poses;
-  }
-  if (tasks > t.task_cap) {
-    t.task_cap = 0;
-    if (track_grow(c, (Xf**)&t.d_c2w, tasks) || track_grow(c, (PoseF**)&t.d_pf, tasks) ||
-        track_grow(c, &t.d_sums, tasks) || track_grow(c, &t.d_cnt, tasks))
-      return MANTIS_ERR_OOM;
-    t.task_cap = tasks;
-  }
+  if (t.d_in.grow(c, in_bytes) || t.h_in.grow(c, in_bytes) || t.d_state.grow(c, (size_t)R) ||
+      t.d_res.grow(c, (size_t)R) || t.h_res.grow(c, (size_t)R) || t.d_Twb.grow(c, poses) || t.d_c2w.grow(c, tasks) ||
+      t.d_pf.grow(c, tasks) || t.d_sums.grow(c, tasks) || t.d_cnt.grow(c, tasks))
+    return MANTIS_ERR_OOM;
   return MANTIS_OK;
 }
 
@@ -222,7 +192,7 @@ mantis_status track_impl(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32
 
   // inputs in one pinned block: predictions, extrinsics, then every rig's
   // gaussians in draw order (rig-major; a rig draws whether or not it ends up tracked)
-  Xf* h_pred = (Xf*)t.h_in;
+  Xf* h_pred = (Xf*)t.h_in.get();
   Xf* h_ext = h_pred + n_rigs;
   float* h_g = (float*)(h_ext + (size_t)n);
   for (int r = 0; r < n_rigs; r++) h_pred[r] = trk::xf_from_mat4(pred + 16 * (size_t)r);
@@ -243,7 +213,7 @@ mantis_status track_impl(Ctx* c, const mantis_image* cams, int32_t n_rigs, int32
   HIP_OK(hipMemcpyAsync(t.d_in, t.h_in, in_bytes, hipMemcpyHostToDevice, c->s));
 
   TrackArgs a;
-  a.pred = (const Xf*)t.d_in;
+  a.pred = (const Xf*)t.d_in.get();
   a.ext = a.pred + n_rigs;
   a.gauss = (const float*)(a.ext + (size_t)n);
   a.st = (TrackState*)t.d_state;
