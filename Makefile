@@ -11,11 +11,11 @@ ARCH ?= gfx950
 HIPFLAGS = -O3 -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fno-slp-vectorize -fPIC -Wall -Wno-unused-function -Wno-unused-variable
 CSRC = mantis_amd/csrc
 
-.PHONY: all product oracle ref tools clean sanitize
+.PHONY: all product oracle ref tools clean sanitize lagcheck
 all: product tools oracle
 
 product: mantis_amd/libmantis_amd.so
-mantis_amd/libmantis_amd.so: $(CSRC)/api.hip $(CSRC)/kernels.hip $(CSRC)/gn_impl.hip $(CSRC)/dense_impl.hip $(wildcard $(CSRC)/*.h) $(CSRC)/mk_rpp_np.inc $(CSRC)/markov_impl.hip $(CSRC)/track_impl.hip $(CSRC)/mk_track.h $(CSRC)/mcl_impl.hip $(CSRC)/mk_mcl.h $(CSRC)/mcl_modes_impl.hip $(CSRC)/mk_mcl_modes.h $(CSRC)/mcl_color_impl.hip $(CSRC)/mk_mcl_color.h $(CSRC)/refine_impl.hip $(CSRC)/refine_robust_impl.hip $(CSRC)/mk_refine.h $(CSRC)/smooth_impl.hip $(CSRC)/mk_smooth.h $(CSRC)/linecal_impl.hip $(CSRC)/mk_linecal.h $(CSRC)/mk_calib.h $(CSRC)/mk_icalib.h $(CSRC)/mcl_refine_impl.hip $(CSRC)/mk_mcl_refine.h $(CSRC)/hostbuf.h include/mantis.h include/mantis_ros.h
+mantis_amd/libmantis_amd.so: $(CSRC)/api.hip $(CSRC)/kernels.hip $(CSRC)/gn_impl.hip $(CSRC)/dense_impl.hip $(wildcard $(CSRC)/*.h) $(CSRC)/mk_rpp_np.inc $(CSRC)/markov_impl.hip $(CSRC)/track_impl.hip $(CSRC)/mk_track.h $(CSRC)/mcl_impl.hip $(CSRC)/mk_mcl.h $(CSRC)/mcl_modes_impl.hip $(CSRC)/mk_mcl_modes.h $(CSRC)/mcl_color_impl.hip $(CSRC)/mk_mcl_color.h $(CSRC)/refine_impl.hip $(CSRC)/refine_robust_impl.hip $(CSRC)/mk_refine.h $(CSRC)/smooth_impl.hip $(CSRC)/lag_impl.hip $(CSRC)/mk_smooth.h $(CSRC)/linecal_impl.hip $(CSRC)/mk_linecal.h $(CSRC)/mk_calib.h $(CSRC)/mk_icalib.h $(CSRC)/mcl_refine_impl.hip $(CSRC)/mk_mcl_refine.h $(CSRC)/hostbuf.h include/mantis.h include/mantis_ros.h
 	$(HIPCC) $(HIPFLAGS) -shared -pthread -o $@ $(CSRC)/api.hip -lrccl
 
 tools: build/libmantis_hostcheck.so tools/libmantis_synth.so
@@ -49,7 +49,15 @@ sanitize: build/san/liboracle.so build/san/libmantis_hostcheck.so tools/libmanti
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
 	python3 -m pytest tests -x -q -m "not gpu" -p no:cacheprovider $(SAN_PYTEST)
 
+# The fixed-lag window's rule (mk_smooth.h marginalize and around it) as a program of its own,
+# under AddressSanitizer + UndefinedBehaviorSanitizer, run directly on the CPU: ends with "lagcheck ok"
+build/lagcheck: tools/lagcheck_main.cpp $(wildcard $(CSRC)/mk_*.h) include/mantis.h
+	mkdir -p build
+	g++ $(SANFLAGS) -o $@ tools/lagcheck_main.cpp
+lagcheck: build/lagcheck
+	build/lagcheck
+
 clean:
 	rm -f mantis_amd/libmantis_amd.so build/libmantis_hostcheck.so tools/libmantis_synth.so
-	rm -rf build/san
+	rm -rf build/san build/lagcheck
 	$(MAKE) -C oracle clean

@@ -1529,6 +1529,96 @@ mantis_status mantis_get_smooth_record(void* ctx, int32_t window, int32_t view, 
 mantis_status mantis_get_smooth_pass(void* ctx, int32_t window, int32_t pass, double* e, double* J, double* prior_e,
                                      double* prior_J, double* delta);
 
+/* ---- Fixed-lag smoothing: a context-held window that marginalises ----
+ * mantis_smooth_batch is a batch call: the caller holds N views of frames and
+ * re-stages all of them on every call. These entries keep the window in the
+ * context (in HBM, as the MCL set): one call per incoming view, and the
+ * information of the view that leaves is carried forward as a Gaussian prior
+ * on the next one, computed on the device by a Schur complement. All addition:
+ * no other entry point, struct, kernel or draw changes, MANTIS_ABI_VERSION
+ * stays 5 (find the entries by name, check the sizes with mantis_lag_sizes).
+ * Nothing is drawn from the cv::RNG; the context's prior pose and the robust
+ * switches are not touched. Other entries may be called between pushes: the
+ * window has its own frames, descriptors and workspaces.
+ *
+ * mantis_lag_reset empties the window and fixes its shape: capacity N (2..256),
+ * cams_per_rig C (1..8, <= max_cams; the N C frames the window keeps do not
+ * count against max_cams) and the smoothing parameters. prior_T (16) with
+ * prior_cov (36), both nullable together, put a prior on the first view; they
+ * are checked as mantis_smooth_batch checks its prior. Nothing is launched.
+ *
+ * mantis_lag_push appends one view of C frames (cams[c], one size, the size of
+ * the first push since the reset; copied into the window's own ring of N C
+ * frames, so the caller's buffers are free when the push returns). motion: the
+ * step from the newest held view to this one (ignored on the first push, where
+ * it may be NULL); an unset motion (|q|^2 < 0.5) puts no factor there. T_start
+ * (16, nullable): where the view starts; NULL: T_newest Delta, formed on the
+ * device by the product of the MCL and track predictions; required on the
+ * first push and after an unset motion. When the window already held N views,
+ * the oldest is first marginalised into a prior on the next one and the rest
+ * shift down:
+ *   from the last push's final pass (the lambda = 0 blocks of pass
+ *   iterations_run, with the factors and the prior of that same pass), H_00 and
+ *   g_0 as assembled and factor 0's whitened Ja, Jb, e:
+ *   Lambda = Jb^T Jb - (Jb^T Ja) H_00^-1 (Ja^T Jb), eta = Jb^T e - (Jb^T Ja)
+ *   H_00^-1 g_0 (Cholesky of H_00, two triangular solves, every dot product in
+ *   ascending index order), x* = -Lambda^-1 eta, T_p = T_1 D(x*), Cov_p =
+ *   sigma_row^2 Lambda^-1 with the translation and cross blocks turned to the
+ *   world frame by R of T_p; symmetric bit for bit. (T_p, Cov_p) has the shape
+ *   and frames of mantis_smooth_batch's prior_T / prior_cov, and its whitener
+ *   is formed on the device as that call's host forms it.
+ * This is a first-order marginal at the leaving view's final linearisation
+ * point; no first-estimate Jacobians are kept. No prior is carried (drop_reason
+ * says why) when step 0 had no factor (1), the last push did not end OK (2), or
+ * H_00 (3), Lambda (4) or Cov_p (5) is not positive definite or not finite.
+ * Then the passes of mantis_smooth_batch run over the views held, each from
+ * the pose it held (the new one from its start): the same kernels on the same
+ * bytes, so a push returns what mantis_smooth_batch returns for those views,
+ * starts, motions and prior. out_views: `capacity` entries, the first
+ * out_result->n_views valid, newest last. Device work: k_lag_slide, then 3 (I +
+ * 1) launches, the C frame copies and one copy of the results (which also
+ * brings back T_p and Cov_p). record = 1: mantis_get_smooth_record / _pass
+ * serve the last push as window 0.
+ *
+ * MANTIS_ERR_ARG (nothing launched, the window unchanged, mantis_last_error
+ * names the field): push before reset, no map, capacity or cams_per_rig out of
+ * range, a smoothing parameter outside its range, a frame size differing from
+ * the first push, a pose or motion that is not finite, a missing T_start where
+ * it is required, a missing motion after the first push, a null pointer. */
+typedef struct mantis_lag_params {
+  int32_t struct_size;     /* sizeof(mantis_lag_params) */
+  int32_t capacity;        /* N, 2..256 */
+  int32_t cams_per_rig;    /* C, 1..8 */
+  int32_t pad;
+  mantis_smooth_params smooth;
+} mantis_lag_params;
+/* capacity 8, one camera, mantis_default_smooth_params */
+void mantis_default_lag_params(mantis_lag_params* p);
+
+typedef struct mantis_lag_info {
+  int64_t pushes;          /* since the reset, this one included */
+  int64_t oldest_stamp_ns; /* cams[0].stamp_ns of the oldest view held */
+  int32_t n_views;         /* views held */
+  int32_t has_prior;       /* this push's solve carried a prior */
+  int32_t drop_reason;     /* 0, or why this push's slide left no prior (above) */
+  int32_t slid;            /* this push marginalised a view out */
+} mantis_lag_info;
+/* sizeof(mantis_lag_params), sizeof(mantis_lag_info) (host only) */
+void mantis_lag_sizes(int32_t* params_bytes, int32_t* info_bytes);
+
+mantis_status mantis_lag_reset(void* ctx, const mantis_lag_params* p, const double* prior_T, const double* prior_cov);
+mantis_status mantis_lag_push(void* ctx, const mantis_image* cams, const mantis_motion* motion, const double* T_start,
+                              mantis_smooth_result* out_result, mantis_smooth_view* out_views,
+                              mantis_lag_info* out_info /* nullable */);
+/* The prior the next push's solve will use (T 16, cov 36, *has 0 / 1; each
+ * nullable): the reset's or the carried one while the window is not full; once
+ * it is full, the marginal of the oldest view held, computed now as the next
+ * push will compute it (one small launch). *reason (nullable): drop_reason. */
+mantis_status mantis_lag_get_prior(void* ctx, double* T, double* cov, int32_t* has, int32_t* reason);
+/* The last push's views again. *n: in, the entries `views` has room for; out,
+ * the views held. MANTIS_ERR_ARG when there is too little room. */
+mantis_status mantis_lag_get_views(void* ctx, mantis_smooth_view* views, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

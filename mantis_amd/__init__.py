@@ -135,6 +135,16 @@ class MantisSmoothView(C.Structure):
                 ("covariance", C.c_double * 36)]
 
 
+class MantisLagParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("capacity", C.c_int32), ("cams_per_rig", C.c_int32), ("pad", C.c_int32),
+                ("smooth", MantisSmoothParams)]
+
+
+class MantisLagInfo(C.Structure):
+    _fields_ = [("pushes", C.c_int64), ("oldest_stamp_ns", C.c_int64), ("n_views", C.c_int32),
+                ("has_prior", C.c_int32), ("drop_reason", C.c_int32), ("slid", C.c_int32)]
+
+
 class MantisRefineRobustParams(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("loss", C.c_int32), ("tuning", C.c_double), ("scale_floor", C.c_double)]
 
@@ -341,6 +351,13 @@ _SIGS = {
                                       C.POINTER(MantisSmoothResult), C.POINTER(MantisSmoothView)]),
     "mantis_get_smooth_record": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
     "mantis_get_smooth_pass": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
+    "mantis_default_lag_params": (None, [C.POINTER(MantisLagParams)]),
+    "mantis_lag_sizes": (None, [C.POINTER(C.c_int32)] * 2),
+    "mantis_lag_reset": (C.c_int, [C.c_void_p, C.POINTER(MantisLagParams), C.c_void_p, C.c_void_p]),
+    "mantis_lag_push": (C.c_int, [C.c_void_p, C.POINTER(MantisImage), C.c_void_p, C.c_void_p,
+                                  C.POINTER(MantisSmoothResult), C.POINTER(MantisSmoothView), C.POINTER(MantisLagInfo)]),
+    "mantis_lag_get_prior": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mantis_lag_get_views": (C.c_int, [C.c_void_p, C.POINTER(MantisSmoothView), C.POINTER(C.c_int32)]),
     "mantis_default_refine_robust_params": (None, [C.c_int32, C.POINTER(MantisRefineRobustParams)]),
     "mantis_refine_robust_sizes": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mantis_refine_set_robust": (C.c_int, [C.c_void_p, C.POINTER(MantisRefineRobustParams)]),
@@ -800,6 +817,68 @@ class Mantis:
                                                J.ctypes.data if J.size else None, pe.ctypes.data, pJ.ctypes.data,
                                                delta.ctypes.data), "get_smooth_pass")
         return e, J, pe, pJ, delta
+
+    # fixed-lag smoothing (mantis_lag_*, include/mantis.h) ----------------------
+    LAG_DROPS = {0: "kept", 1: "no_factor", 2: "not_ok", 3: "h00", 4: "lambda", 5: "cov"}
+
+    def lag_params(self, capacity=None, cams_per_rig=None, **smooth):
+        """mantis_default_lag_params, then the overrides (`smooth`: fields of the embedded MantisSmoothParams)."""
+        p = MantisLagParams()
+        lib().mantis_default_lag_params(C.byref(p))
+        if capacity is not None:
+            p.capacity = capacity
+        if cams_per_rig is not None:
+            p.cams_per_rig = cams_per_rig
+        for k, v in smooth.items():
+            if k not in dict(MantisSmoothParams._fields_) or k == "struct_size":
+                raise TypeError(f"lag: unknown parameter {k!r}")
+            setattr(p.smooth, k, v)
+        return p
+
+    def lag_reset(self, capacity=None, cams_per_rig=None, prior_T=None, prior_cov=None, **smooth):
+        """mantis_lag_reset: empty the window and fix its shape; prior_T (4 x 4) with prior_cov (6 x 6): the
+        optional prior on the first view."""
+        p = self.lag_params(capacity, cams_per_rig, **smooth)
+        pT = None if prior_T is None else np.ascontiguousarray(prior_T, np.float64).reshape(16)
+        pC = None if prior_cov is None else np.ascontiguousarray(prior_cov, np.float64).reshape(36)
+        self._chk(lib().mantis_lag_reset(self.h, C.byref(p), None if pT is None else pT.ctypes.data,
+                                         None if pC is None else pC.ctypes.data), "lag_reset")
+        self._lag = p
+
+    def lag_push(self, images, motion=None, T_start=None):
+        """mantis_lag_push: one view of cams_per_rig images. motion: delta_pos | delta_quat_xyzw (7), the step
+        from the newest held view (None only on the first push; a zero quaternion: no factor). T_start (4 x 4):
+        None lets the device form T_newest Delta. Returns (result, views held [newest last], info)."""
+        p = getattr(self, "_lag", None)
+        if p is None:
+            raise MantisError("lag_push: no lag_reset on this context")
+        cams = (MantisImage * len(images))(*images)
+        mo = None if motion is None else np.ascontiguousarray(motion, np.float64).reshape(7)
+        T = None if T_start is None else np.ascontiguousarray(T_start, np.float64).reshape(16)
+        out, info = MantisSmoothResult(), MantisLagInfo()
+        vw = (MantisSmoothView * p.capacity)()
+        self._chk(lib().mantis_lag_push(self.h, cams, None if mo is None else mo.ctypes.data,
+                                        None if T is None else T.ctypes.data, C.byref(out), vw, C.byref(info)), "lag_push")
+        self._smooth_shape = (out.n_views, p.cams_per_rig * out.n_cand)
+        return out, [vw[k] for k in range(out.n_views)], info
+
+    def lag_prior(self):
+        """mantis_lag_get_prior: (has, T [4, 4], cov [6, 6], drop_reason) of the prior the next push's solve will use."""
+        T, cov = np.zeros((4, 4)), np.zeros((6, 6))
+        has, why = C.c_int32(0), C.c_int32(0)
+        self._chk(lib().mantis_lag_get_prior(self.h, T.ctypes.data, cov.ctypes.data, C.byref(has), C.byref(why)),
+                  "lag_get_prior")
+        return bool(has.value), T, cov, why.value
+
+    def lag_views(self):
+        """mantis_lag_get_views: the last push's views again."""
+        p = getattr(self, "_lag", None)
+        if p is None:
+            raise MantisError("lag_views: no lag_reset on this context")
+        vw = (MantisSmoothView * p.capacity)()
+        n = C.c_int32(p.capacity)
+        self._chk(lib().mantis_lag_get_views(self.h, vw, C.byref(n)), "lag_get_views")
+        return [vw[k] for k in range(n.value)]
 
     REFINE_LOSSES = {None: 0, "none": 0, "huber": 1, "tukey": 2}
 

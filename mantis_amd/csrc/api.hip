@@ -447,6 +447,32 @@ struct Ctx : CtxStreams {
     int windows = 0, N = 0, C = 0, P = 0, record = 0, cands = 0, lay_F = 0;  // the last call
     std::vector<int32_t> runs;  // its windows' iterations_run
   } sm;
+  const Smooth* sm_rec = nullptr;  // whose record mantis_get_smooth_record / _pass serve: sm, or the last push's lag.ws
+  // the fixed-lag window (lag_impl.hip): the whole state lives in HBM between the pushes. ws.d_out:
+  // the head (window result, T_p / W_p / Cov_p), the views' RefineRig in time order and the final
+  // blocks (one copy back per push); ws.d_in: what a push uploads; ws.d_work / d_slots: the window
+  // workspace in mantis_smooth_batch's layout. Allocated at the first push since a reset, released
+  // by a reset that changes the shape, freed with the context.
+  struct Lag {
+    bool live = false;  // a reset has run
+    mantis_lag_params p{};
+    Smooth ws;
+    DevBuf<double> d_D;          // capacity x 16: Transform of step k
+    DevBuf<int32_t> d_has;       // capacity: step k has a factor
+    DevBuf<GnCam> d_gncam;       // capacity x C, time order
+    DevBuf<FrameDesc> d_fd;      // capacity x C, time order, pointing into the ring
+    DevBuf<uint8_t> d_ring;      // capacity x C frames of W x H x 3
+    int cap = 0, C = 0, I = -1, W = 0, H = 0;  // the shape the buffers were allocated for (cap = 0: none)
+    int n = 0;                   // views held
+    int64_t pushes = 0;
+    bool last_ok = false;        // the last push ended OK
+    int has_prior = 0, drop_reason = 0;  // of the last push's solve (before any: the reset's prior)
+    bool reset_prior = false;    // a prior of the reset waits for the first push
+    double Tp[16], Wp[36], Cov[36];      // host copy of the prior the last solve used (or the reset's)
+    std::vector<int32_t> has;    // host copy of d_has
+    std::vector<int64_t> stamps; // of the views held
+    std::vector<mantis_smooth_view> views;  // the last push's
+  } lag;
 };
 
 // Camera-sharded calls: every rank must enter the same collectives in the same
@@ -2286,6 +2312,7 @@ mantis_status mantis_set_profiling(void* ctx, int32_t on) {
 #include "mcl_color_impl.hip"
 #include "refine_impl.hip"
 #include "smooth_impl.hip"
+#include "lag_impl.hip"
 #include "linecal_impl.hip"
 #include "mcl_refine_impl.hip"
 #include "ros_wire.h"

@@ -1046,6 +1046,115 @@ int hc_smooth_seq(int N, const double* T_in, const double* motions, const double
   }
   return 1;
 }
+// The fixed-lag window (mk_smooth.h, lag_impl.hip): the rules k_lag_slide runs.
+// the marginal of view 0 on view 1 and its whitener; returns the drop reason (0: a prior is carried)
+int hc_lag_marginalize(const double* H00, const double* g0, const double* Ja, const double* Jb, const double* e,
+                       const double* T1, double sigma_row, double* Tp, double* Cov, double* Wp) {
+  return mk::smooth::marginal_prior(H00, g0, Ja, Jb, e, T1, sigma_row, Tp, Cov, Wp);
+}
+// marginalize alone: Lambda's inverse scaled and turned, without the whitener's verdict
+int hc_lag_marginal(const double* H00, const double* g0, const double* Ja, const double* Jb, const double* e,
+                    const double* T1, double sigma_row, double* Tp, double* Cov) {
+  return mk::smooth::marginalize(H00, g0, Ja, Jb, e, T1, sigma_row, Tp, Cov);
+}
+int hc_lag_schur(const double* H00, const double* g0, const double* Ja, const double* Jb, const double* e, double* Lam,
+                 double* eta) {
+  return mk::smooth::schur0(H00, g0, Ja, Jb, e, Lam, eta);
+}
+int hc_lag_whitener(const double* cov, double sigma_row, double* Wp) {
+  return mk::smooth::prior_whitener(cov, sigma_row, Wp) ? 1 : 0;
+}
+void hc_lag_predict(const double* T_newest, const double* D, double* T) { mk::smooth::predict_start(T_newest, D, T); }
+// A push sequence on host frames, as mantis_lag_reset + n_push x mantis_lag_push run it: frames
+// [push][C], T_start [push][16] with has_start [push], motions [push][7] (row 0 unused), the reset's
+// prior (nullable). Per push: out [push], views [push][cap], info [push][4] = views held, has_prior,
+// drop_reason, slid, and prior [push][52] = T_p | Cov_p of the push's solve. Returns 0 when the
+// reset's prior is refused or a start is missing where it is required.
+int hc_lag_seq(int n_push, int cap, const double* T_start, const int32_t* has_start, const double* motions,
+               const double* prior_T, const double* prior_cov, const double* Tbc, const double* K, const double* D,
+               const uint8_t* const* frames, int C, int W, int H, const double* X, int nw, int nr, int ng,
+               const mantis_smooth_params* p, mantis_smooth_result* out, mantis_smooth_view* views, int32_t* info,
+               double* prior) {
+  namespace rf = mk::refine;
+  namespace sm = mk::smooth;
+  const int nl = nw + nr + ng;
+  std::vector<uint8_t> flags(nl > 0 ? nl : 1);
+  rf::line_flags(X, nl, p->landmark_pitch, flags.data());
+  std::vector<int32_t> cand(nl > 0 ? nl : 1);
+  const int nc = rf::candidates(flags.data(), nl, cand.data());
+  std::vector<mk::GnCam> gc(C);
+  std::vector<mk::Cam> cm(C);
+  for (int c = 0; c < C; c++) {
+    rf::gncam_from(Tbc + 16 * c, gc[c]);
+    cm[c] = hc_cam(K + 9 * c, D + 4 * c);
+  }
+  double Tp[16] = {0}, Wp[36] = {0}, Cov[36] = {0};
+  int hp = 0;
+  if (prior_T) {
+    if (!sm::prior_whitener(prior_cov, p->sigma_row, Wp)) return 0;
+    std::memcpy(Tp, prior_T, sizeof(Tp));
+    std::memcpy(Cov, prior_cov, sizeof(Cov));
+    hp = 1;
+  }
+  std::vector<double> T, Dm;  // the poses held (n x 16), the steps' Transforms (cap x 16)
+  std::vector<int32_t> has(cap, 0);
+  std::vector<const uint8_t*> fr;
+  Dm.assign(16 * (size_t)cap, 0.0);
+  std::vector<sm::PassRecord> rec;
+  bool last_ok = false;
+  for (int q = 0; q < n_push; q++) {
+    int n = (int)(T.size() / 16), why = sm::kLagKept, slid = 0;
+    double Dn[16] = {0};
+    const int hm = q > 0 ? hc_smooth_motion(motions + 7 * q, motions + 7 * q + 3, Dn) : 0;
+    if (!has_start[q] && (n == 0 || !hm)) return 0;
+    double Ts[16];
+    if (has_start[q]) std::memcpy(Ts, T_start + 16 * (size_t)q, sizeof(Ts));
+    else sm::predict_start(&T[16 * (size_t)(n - 1)], Dn, Ts);
+    if (n == cap) {
+      slid = 1;
+      why = !has[0] ? sm::kLagNoFactor : !last_ok ? sm::kLagNotOk : sm::kLagKept;
+      if (why == sm::kLagKept) {
+        const sm::PassRecord& P = rec.back();
+        double Hd[36], Ho[36], g[6];
+        sm::assemble(0, n, P.acc28.data(), has.data(), P.e.data(), P.J.data(), hp, P.pe.data(), P.pJ.data(), 0.0, Hd, Ho, g);
+        why = sm::marginal_prior(Hd, g, P.J.data(), P.J.data() + 36, P.e.data(), &T[16], p->sigma_row, Tp, Cov, Wp);
+      } else {
+        for (int e = 0; e < 16; e++) Tp[e] = e % 5 == 0 ? 1.0 : 0.0;
+        for (int e = 0; e < 36; e++) Cov[e] = Wp[e] = 0.0;
+      }
+      hp = why == sm::kLagKept;
+      T.erase(T.begin(), T.begin() + 16);
+      Dm.erase(Dm.begin(), Dm.begin() + 16);
+      Dm.resize(16 * (size_t)cap, 0.0);
+      has.erase(has.begin());
+      has.push_back(0);
+      fr.erase(fr.begin(), fr.begin() + C);
+      n--;
+    }
+    T.insert(T.end(), Ts, Ts + 16);
+    if (n > 0) {
+      std::memcpy(&Dm[16 * (size_t)(n - 1)], Dn, sizeof(Dn));
+      has[n - 1] = hm;
+    }
+    for (int c = 0; c < C; c++) fr.push_back(frames[(size_t)q * C + c]);
+    n++;
+    mantis_smooth_view* V = views + (size_t)q * cap;
+    sm::smooth_seq(n, T.data(), Dm.data(), has.data(), hp, Tp, Wp, gc.data(), cm.data(), fr.data(), C, W, H, X, nw, nr,
+                   cand.data(), nc, *p, out[q], V, &rec);
+    for (int k = 0; k < n; k++) std::memcpy(&T[16 * (size_t)k], V[k].T_w_b, sizeof(double) * 16);
+    last_ok = out[q].status == sm::kOk;
+    info[4 * q] = n;
+    info[4 * q + 1] = hp;
+    info[4 * q + 2] = why;
+    info[4 * q + 3] = slid;
+    std::memcpy(prior + 52 * (size_t)q, Tp, sizeof(Tp));
+    std::memcpy(prior + 52 * (size_t)q + 16, Cov, sizeof(Cov));
+  }
+  return 1;
+}
+int hc_sizeof_lag_params(void) { return (int)sizeof(mantis_lag_params); }
+int hc_sizeof_lag_info(void) { return (int)sizeof(mantis_lag_info); }
+
 int hc_sizeof_smooth_params(void) { return (int)sizeof(mantis_smooth_params); }
 int hc_sizeof_smooth_result(void) { return (int)sizeof(mantis_smooth_result); }
 int hc_sizeof_smooth_view(void) { return (int)sizeof(mantis_smooth_view); }

@@ -5,9 +5,12 @@
 // log_so3 / J_r^-1, the between and prior factors with their Jacobians for the
 // right perturbation of calib::right_update, the assembly of the 6 x 6 blocks,
 // the block Cholesky with its substitutions, the window's figures and gates,
-// and (host) the marginal covariances. Shared by the device (k_smooth_acc /
-// k_smooth_solve, smooth_impl.hip) and the host build of the CPU tests
-// (hostcheck.cpp hc_smooth_*, tools/smoothcheck_main.cpp). Both builds keep
+// (host) the marginal covariances, and for the fixed-lag window (mantis_lag_*,
+// lag_impl.hip) the marginal of the leaving view, the whitener of the prior it
+// leaves and the predicted start. Shared by the device (k_smooth_acc /
+// k_smooth_solve, smooth_impl.hip; k_lag_slide, lag_impl.hip) and the host
+// build of the CPU tests (hostcheck.cpp hc_smooth_* / hc_lag_*,
+// tools/smoothcheck_main.cpp, tools/lagcheck_main.cpp). Both builds keep
 // -ffp-contract=off, and every sum here runs in a stated order.
 #pragma once
 #include <cmath>
@@ -15,6 +18,7 @@
 #include <vector>
 
 #include "mk_calib.h"
+#include "mk_track.h"
 
 namespace mk {
 namespace smooth {
@@ -163,9 +167,11 @@ MK_HD void prior(const double* T0, const double* Tp, const double* Wp, double* e
   }
 }
 
-// Host: Wp = sigma_row L_c^-1 of a covariance (36, row-major), Cov = L_c L_c^T
-// by chol6. False when the covariance is not finite or not positive definite.
-inline bool prior_whitener(const double* cov, double sigma_row, double* Wp) {
+// Wp = sigma_row L_c^-1 of a covariance (36, row-major), Cov = L_c L_c^T by
+// chol6. False when the covariance is not finite or not positive definite. The
+// host forms the whitener of a caller's prior with it, the device (k_lag_slide)
+// that of a marginalised one: the same operations, the same bytes.
+MK_HD bool prior_whitener(const double* cov, double sigma_row, double* Wp) {
   for (int e = 0; e < 36; e++)
     if (!std::isfinite(cov[e])) return false;
   double L[36];
@@ -181,6 +187,130 @@ inline bool prior_whitener(const double* cov, double sigma_row, double* Wp) {
     if (!std::isfinite(Wp[e])) return false;
   }
   return true;
+}
+
+// ---- The fixed-lag window (mantis_lag_push): view 0 leaves as a prior on view 1 ----
+// Why a prior is, or is not, carried into a window (mantis_lag_info.drop_reason)
+constexpr int kLagKept = 0;      // a prior is carried, or none was due (the window was not full)
+constexpr int kLagNoFactor = 1;  // step 0 had no factor: the chain is broken there
+constexpr int kLagNotOk = 2;     // the last push did not end OK
+constexpr int kLagH00 = 3;       // H_00 is not positive definite
+constexpr int kLagLambda = 4;    // the Schur complement is not positive definite
+constexpr int kLagCov = 5;       // Cov_p is not finite or not positive definite
+
+// The marginal of view 0 on view 1, from the final pass's blocks of a window
+// that ended OK (lambda = 0): H00 / g0 as assembled (A_0 + Ja^T Ja + the
+// prior's term; b_0 + Ja^T e + the prior's), factor 0's whitened Ja, Jb, e and
+// view 1's final pose T1.
+//   B = Jb^T Ja, L0 = chol6(H00), Y = L0^-1 B^T, z = L0^-1 g0   (two triangular solves)
+//   Lambda = Jb^T Jb - Y^T Y,  eta = Jb^T e - Y^T z
+//   x* = -Lambda^-1 eta (chol6),  T_p = T1 D(x*) (calib::right_update)
+//   Cov_p = sigma_row^2 Lambda^-1 = sigma_row^2 L^-T L^-1, its translation and
+//   cross blocks turned to the world frame by R of T_p (B C B^T, B = diag(R_p,
+//   I), as conclude turns its covariances).
+// Every dot product runs in ascending index order; Lambda and Cov_p are formed
+// as upper triangles and mirrored, so both are symmetric bit for bit. (T_p,
+// Cov_p) has the shape and frames of mantis_smooth_batch's prior_T / prior_cov.
+// This is a first-order marginal at the leaving view's final linearisation
+// point: view 1 keeps being relinearised afterwards, and no first-estimate
+// Jacobians are kept for it.
+// schur0: Lambda (36) and eta (6); kLagKept or kLagH00.
+MK_HD int schur0(const double* H00, const double* g0, const double* Ja, const double* Jb, const double* e, double* Lam,
+                 double* eta) {
+  double L0[36], B[36], Y[36], z[6];
+  if (!calib::chol6(H00, L0)) return kLagH00;
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) {
+      double s = 0;
+      for (int r = 0; r < 6; r++) s += Jb[6 * r + i] * Ja[6 * r + j];
+      B[6 * i + j] = s;
+    }
+  for (int c = 0; c < 6; c++)  // column c of Y: L0 Y = B^T
+    for (int i = 0; i < 6; i++) {
+      double s = B[6 * c + i];
+      for (int k = 0; k < i; k++) s -= L0[6 * i + k] * Y[6 * k + c];
+      Y[6 * i + c] = s / L0[6 * i + i];
+    }
+  for (int i = 0; i < 6; i++) {
+    double s = g0[i];
+    for (int k = 0; k < i; k++) s -= L0[6 * i + k] * z[k];
+    z[i] = s / L0[6 * i + i];
+  }
+  for (int i = 0; i < 6; i++) {
+    for (int j = i; j < 6; j++) {
+      double s = 0;
+      for (int r = 0; r < 6; r++) s += Jb[6 * r + i] * Jb[6 * r + j];
+      for (int m = 0; m < 6; m++) s -= Y[6 * m + i] * Y[6 * m + j];
+      Lam[6 * i + j] = Lam[6 * j + i] = s;
+    }
+    double s = 0;
+    for (int r = 0; r < 6; r++) s += Jb[6 * r + i] * e[r];
+    for (int m = 0; m < 6; m++) s -= Y[6 * m + i] * z[m];
+    eta[i] = s;
+  }
+  return kLagKept;
+}
+// marginalize: (T_p, Cov_p); kLagKept, or the reason for no prior (Tp / Cov are then not to be used; whether
+// Cov_p is finite and positive definite is prior_whitener's verdict, in marginal_prior).
+MK_HD int marginalize(const double* H00, const double* g0, const double* Ja, const double* Jb, const double* e,
+                      const double* T1, double sigma_row, double* Tp, double* Cov) {
+  double Lam[36], eta[6], L[36], Li[36], x[6], S[36];
+  if (schur0(H00, g0, Ja, Jb, e, Lam, eta) != kLagKept) return kLagH00;
+  if (!calib::chol6(Lam, L)) return kLagLambda;
+  for (int i = 0; i < 6; i++) eta[i] = -eta[i];
+  calib::chol6_solve(L, eta, 1, x, 1);
+  for (int q = 0; q < 16; q++) Tp[q] = T1[q];
+  calib::right_update(Tp, x);
+  for (int c = 0; c < 6; c++)  // column c of L^-1 by forward substitution
+    for (int i = 0; i < 6; i++) {
+      double s = i == c ? 1.0 : 0.0;
+      for (int k = 0; k < i; k++) s -= L[6 * i + k] * Li[6 * k + c];
+      Li[6 * i + c] = s / L[6 * i + i];
+    }
+  const double s2 = sigma_row * sigma_row;
+  for (int i = 0; i < 6; i++)
+    for (int j = i; j < 6; j++) {
+      double s = 0;
+      for (int m = j; m < 6; m++) s += Li[6 * m + i] * Li[6 * m + j];  // L^-1 is lower: the terms below m = j are zeros
+      S[6 * i + j] = S[6 * j + i] = s2 * s;
+    }
+  double R[9], t[3], M[9];
+  rt_of(Tp, R, t);
+  for (int i = 0; i < 3; i++)
+    for (int b = 0; b < 3; b++) M[3 * i + b] = R[3 * i] * S[b] + R[3 * i + 1] * S[6 + b] + R[3 * i + 2] * S[12 + b];
+  for (int i = 0; i < 3; i++) {
+    for (int j = i; j < 3; j++) Cov[6 * i + j] = M[3 * i] * R[3 * j] + M[3 * i + 1] * R[3 * j + 1] + M[3 * i + 2] * R[3 * j + 2];
+    for (int j = 0; j < 3; j++)
+      Cov[6 * i + 3 + j] = R[3 * i] * S[3 + j] + R[3 * i + 1] * S[6 + 3 + j] + R[3 * i + 2] * S[12 + 3 + j];
+    for (int j = i; j < 3; j++) Cov[6 * (3 + i) + 3 + j] = S[6 * (3 + i) + 3 + j];
+  }
+  for (int i = 0; i < 6; i++)
+    for (int j = i + 1; j < 6; j++) Cov[6 * j + i] = Cov[6 * i + j];
+  return kLagKept;
+}
+
+// The prior a slide leaves: marginalize, then the whitener of Cov_p. Wp = 0, Tp
+// = I and Cov = 0 with the reason when none is carried (a zero whitener adds
+// exact zeros to H_00, g_0 and the cost).
+MK_HD int marginal_prior(const double* H00, const double* g0, const double* Ja, const double* Jb, const double* e,
+                         const double* T1, double sigma_row, double* Tp, double* Cov, double* Wp) {
+  int why = marginalize(H00, g0, Ja, Jb, e, T1, sigma_row, Tp, Cov);
+  if (why == kLagKept) {
+    bool fin = true;
+    for (int q = 0; q < 16; q++) fin = fin && std::isfinite(Tp[q]);
+    if (!fin || !prior_whitener(Cov, sigma_row, Wp)) why = kLagCov;
+  }
+  if (why != kLagKept) {
+    for (int q = 0; q < 16; q++) Tp[q] = q % 5 == 0 ? 1.0 : 0.0;
+    for (int q = 0; q < 36; q++) Cov[q] = Wp[q] = 0.0;
+  }
+  return why;
+}
+
+// The start of a pushed view when the caller gives none: T_newest Delta by
+// xf_mul (mk_math.h), the product of the MCL and track predictions.
+MK_HD void predict_start(const double* T_newest, const double* D, double* T) {
+  track::xf_to_mat4(xf_mul(track::xf_from_mat4(T_newest), track::xf_from_mat4(D)), T);
 }
 
 // H += J^T J and g += J^T e of one 6-row factor, each entry summed over the rows in ascending order

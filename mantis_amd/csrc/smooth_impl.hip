@@ -349,6 +349,7 @@ mantis_status smooth_impl(Ctx* c, const mantis_image* cams, int32_t Wn, int32_t 
   Ctx::Smooth& r = c->sm;
   Ctx::Refine& rf = c->rf;
   r.windows = 0;  // no record until this call has finished
+  c->sm_rec = &r;
   if (mantis_status e = refine_flags(c, p->landmark_pitch)) return e;
   const int n_cand = rf.n_cand;
   const SmoothLayout L = smooth_layout(V, Wn, F, (size_t)I + 1);
@@ -523,7 +524,7 @@ mantis_status mantis_get_smooth_record(void* ctx, int32_t window, int32_t view, 
   Ctx* c = (Ctx*)ctx;
   if (!c) return MANTIS_ERR_ARG;
   bind_device(c);
-  const Ctx::Smooth& r = c->sm;
+  const Ctx::Smooth& r = c->sm_rec ? *c->sm_rec : c->sm;  // the last smooth call: a batch call, or a push (lag_impl.hip)
   if (!r.windows || !r.record) {
     c->err = "smooth record: the last smooth call kept none (params.record = 1)";
     return MANTIS_ERR_STATE;
@@ -546,7 +547,7 @@ mantis_status mantis_get_smooth_pass(void* ctx, int32_t window, int32_t pass, do
   Ctx* c = (Ctx*)ctx;
   if (!c) return MANTIS_ERR_ARG;
   bind_device(c);
-  const Ctx::Smooth& r = c->sm;
+  const Ctx::Smooth& r = c->sm_rec ? *c->sm_rec : c->sm;  // the last smooth call: a batch call, or a push (lag_impl.hip)
   if (!r.windows || !r.record) {
     c->err = "smooth pass: the last smooth call kept none (params.record = 1)";
     return MANTIS_ERR_STATE;
